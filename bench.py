@@ -5,7 +5,7 @@ BASELINE.json configs[1] (`BCNN_S2.yaml on 1xMI355X`).
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
-(the first form with N > 1 re-executes itself as the second one: one process per GPU over RCCL)
+(the first form with N > 1 starts the second one as a child: one process per GPU over RCCL)
 
 One step = one minibatch already resident in HBM -> model forward (VGG-16 on
 MIOpen, bilinear pooling on the gfx950 kernels) -> CrossEntropy(label_smoothing
@@ -13,11 +13,17 @@ MIOpen, bilinear pooling on the gfx950 kernels) -> CrossEntropy(label_smoothing
 throughout (the reference's dtype; parity target 1e-4).  Weak scaling: every
 rank trains batch 64; `value` = all images of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE short JSON line as the LAST line of stdout (< 4 KB: `final_line`).  At N=1 it also carries
-  roofline     - the dominant hand-written kernel of the step: algorithmic FLOPs / HIP-event time
-  cpu_baseline - the oracle's BCNN (reference algorithm on the torch CPU path) timed on the host cores
-Everything else (per-kernel rows of the pooling head, the other BASELINE.json configs, the DDP bucket timeline) goes
-to gpurun_out/bench_detail.json and, as a short table, to stderr - never onto the line the driver parses.
+Rank 0 prints ONE short JSON line as the LAST line of stdout (< 4 KB: `final_line`).  A plain run does only what that
+line's headline needs: set up, warm up, time --steps steps, write the last step's outputs (--dump-outputs DIR), print.
+  --dump-outputs DIR  after the timed steps: DIR/<name>.npy (float32) of what the last timed step computed - the loss, the
+                      model's outputs and a fixed, seeded sample of every updated parameter (< 64 MB in all); the inputs
+                      are seeded, so two builds run with the same arguments can be compared output for output
+  --full              also measure everything beyond the headline.  At N=1 the line then carries
+    roofline     - the dominant hand-written kernel of the step: algorithmic FLOPs / HIP-event time
+    cpu_baseline - the oracle's BCNN (reference algorithm on the torch CPU path) timed on the host cores
+  and everything else (per-kernel rows of the pooling head, the other BASELINE.json configs, the hipGraph rows, the DDP
+  bucket timeline) goes to the detail file (`emit`: $HAWKEYE_BENCH_DETAIL, else its default path) and, as a short table,
+  to stderr - never onto the line the driver parses.
 """
 import argparse
 import ctypes
@@ -64,11 +70,19 @@ def parse():
     ap.add_argument('--ddp-trace', action='store_true', help='N > 1: add `ddp_timeline` (where in the backward each '
                                                              'gradient bucket\'s all-reduce was issued)')
     ap.add_argument('--kernels-first', action='store_true',
-                    help='also time the pooling-head kernels BEFORE the training loop (`kernels_before`): the same kernels read '
-                         '1.2-1.4x slower right after 25 conv-bound steps (power-limited clocks) than on a cool chip')
+                    help='--full: also time the pooling-head kernels BEFORE the training loop (`kernels_before`): the same '
+                         'kernels read 1.2-1.4x slower right after 25 conv-bound steps (power-limited clocks) than on a cool chip')
     ap.add_argument('--no-other-models', action='store_true',
                     help='skip the subprocess that times the other BASELINE.json configs (MPN, CBCNN, APCNN-8142)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure what it does not need: per-kernel rooflines, the CPU baseline, the '
+                         'other configs, the hipGraph rows, the DDP bucket timeline (the --no-* options above trim this)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32)')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def free_port():
@@ -103,9 +117,10 @@ def gather_rank_devices(rank, world, dev):
 
 
 def respawn_one_rank_per_gpu(a):
-    """`python bench.py --gpus N` with N > 1 and no torchrun environment: become
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` (one process per
-    GPU; rank 0 prints the JSON line).  Replaces train.py:220-228's single-process nn.DataParallel."""
+    """`python bench.py --gpus N` with N > 1 and no torchrun environment: run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a child (one process
+    per GPU; rank 0 prints the JSON line) and exit with its status.  A child, not an exec: this process has already asked
+    the runtime for the device count.  Replaces train.py:220-228's single-process nn.DataParallel."""
     if not a.share_gpu and torch.cuda.device_count() < a.gpus:
         sys.exit(f'bench.py: --gpus {a.gpus} but only {torch.cuda.device_count()} GPU(s) visible '
                  f'(--share-gpu --backend gloo runs the ranks on one GPU for a functional check)')
@@ -115,7 +130,10 @@ def respawn_one_rank_per_gpu(a):
     # host threads: N ranks x (all cores) OpenMP threads oversubscribe the host (the optimiser's foreach kernels and the
     # pinned-memory copies run on them); give each rank its share before torch is imported in the children
     env.setdefault('OMP_NUM_THREADS', str(host_threads_per_rank(a.gpus)))
-    os.execve(sys.executable, cmd, env)
+    import subprocess
+    sys.stdout.flush()
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)            # killed by a signal: the shell's 128 + signal
 
 
 def build_model(name, classes):
@@ -348,6 +366,41 @@ def graph_rows(timeout_s=200):
         return {'error': repr(e)[:300]}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def output_tensors(obj, name='output'):
+    """(name, tensor) for every tensor in a model's output: a tensor, or tuples / lists / dicts of them."""
+    if torch.is_tensor(obj):
+        return [(name, obj)]
+    if isinstance(obj, dict):
+        return [r for k, v in obj.items() for r in output_tensors(v, f'{name}.{k}')]
+    if isinstance(obj, (list, tuple)):
+        return [r for i, v in enumerate(obj) for r in output_tensors(v, f'{name}.{i}')]
+    return []
+
+
+def dump_outputs(path, loss, out, model):
+    """What the last timed step computed, as DIR/<name>.npy in float32: `loss`, `output[.i...]` (the model's outputs) and
+    `param.<name>` (every parameter after the optimiser step).  An array larger than `cap` elements is replaced by a fixed,
+    seeded sample of `cap` of its elements (the same indices in every run), so the files stay under DUMP_MAX_BYTES."""
+    import numpy as np
+    arrays = [('loss', loss.detach().reshape(1))] + [(n, t.detach()) for n, t in output_tensors(out)] + \
+             [('param.' + n, p.detach()) for n, p in model.named_parameters()]
+    cap = max(1024, min(1 << 20, DUMP_MAX_BYTES // 4 // len(arrays)))
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for i, (name, t) in enumerate(arrays):
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(i)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = np.ascontiguousarray(t.float().cpu().numpy(), dtype=np.float32)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, (name, total)
+        np.save(os.path.join(path, name + '.npy'), a)
+    return total
+
+
 LINE_KEYS = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
              'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'ddp')
 LINE_MAX = 4096
@@ -473,9 +526,9 @@ def main():
                 else CINLoss(CfgNode(dict(alpha=2.0, beta=0.5))).to(dev))
         params += list(crit.parameters())
     opt = torch.optim.SGD(params, lr=0.005, momentum=0.9, weight_decay=1e-5)   # configs/BCNN_S2
-    # (the bucket timeline is always recorded with more than one rank: the first multi-GPU run then shows where in the
-    #  backward each all-reduce was issued without a code change)
-    reducer = ddp.GradientAllReducer(model, trace=a.force_pg or a.ddp_trace or world > 1) if use_pg else None
+    # (with --full the bucket timeline is always recorded with more than one rank: where in the backward each all-reduce
+    #  was issued, without a code change)
+    reducer = ddp.GradientAllReducer(model, trace=a.force_pg or a.ddp_trace or (a.full and world > 1)) if use_pg else None
 
     g = torch.Generator(device=dev).manual_seed(rank)
     images = torch.randn(a.batch, 3, a.image, a.image, device=dev, generator=g)
@@ -485,7 +538,7 @@ def main():
     if a.model in ('OSMENet', 'CIN'):                      # class-balanced batches (pairs of samples per class)
         labels = (torch.arange(a.batch, device=dev) // 2) % a.classes
 
-    def step():
+    def step(keep=False):
         out = model(images, labels) if a.model == 'APCNN' else model(images)
         loss = sum(crit(o, labels) for o in out[1]) if a.model == 'APCNN' else crit(out, labels)   # tuples: MAMC / CIN
         if reducer is not None:
@@ -496,10 +549,10 @@ def main():
         if reducer is not None:
             reducer.finish()
         opt.step()
-        return loss
+        return loss, (out if keep else None)       # keep: the outputs of the step --dump-outputs writes
 
     kernels_before = None
-    if a.kernels_first and world == 1:
+    if a.full and a.kernels_first and world == 1:
         kernels_before = kernel_rooflines(a.batch, 512, (a.image // 32) ** 2, dev)
     for i in range(a.warmup):
         tw = time.perf_counter()
@@ -511,8 +564,8 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        loss = step()
+    for i in range(a.steps):
+        loss, out = step(keep=a.dump_outputs is not None and i == a.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -537,7 +590,9 @@ def main():
                        'memory_format': 'channels_last' if a.channels_last else 'contiguous'},
         }
         detail = {}
-        if world == 1 and not a.no_kernels:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, loss, out, model)
+        if a.full and world == 1 and not a.no_kernels:
             ks = kernel_rooflines(a.batch, 512, (a.image // 32) ** 2, dev)
             # the step's longest single hand-written launch sequence (stage entry points and multi-launch sums excluded)
             dom = max((k for k in ks if k['shipped_kernel']), key=lambda k: k['us'])
@@ -556,7 +611,7 @@ def main():
             detail['kernels'] = ks
             if kernels_before is not None:
                 detail['kernels_before'] = kernels_before
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(a.image, a.classes)
         if reducer is not None and reducer.trace:
             tl = reducer.timeline()
@@ -576,7 +631,7 @@ def main():
                 detail['rccl'] = ddp.rccl_summary(max_lines=40)
                 res.setdefault('ddp', {})['rccl'] = {k: rs[k] for k in ('version', 'channels', 'rings', 'trees', 'transports')} | \
                     {'tuning': [t[:80] for t in rs['tuning']]}
-        if world == 1 and not a.no_other_models and a.model == 'BCNN' and not a.force_pg:
+        if a.full and world == 1 and not a.no_other_models and a.model == 'BCNN' and not a.force_pg:
             torch.cuda.empty_cache()
             detail['other_models'] = other_models()
             detail['graph_rows'] = graph_rows()

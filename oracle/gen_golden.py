@@ -25,7 +25,7 @@ sys.path.insert(0, REF)
 sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
 sys.path.insert(0, HERE)
 
-from inputs import rs_randn, rs_relu_randn, rs_signed_channels, sub  # noqa: E402  (tests/golden/inputs.py)
+from inputs import rs_randn, rs_relu_randn, rs_signed_channels, save_golden, sub  # noqa: E402  (tests/golden/inputs.py)
 
 torch.manual_seed(0)
 torch.set_num_threads(8)
@@ -47,9 +47,8 @@ def t(a):
 
 
 def save(name, **arrs):
-    np.savez_compressed(os.path.join(OUT, name + '.npz'),
-                        **{k: (v.detach().numpy() if torch.is_tensor(v) else np.asarray(v))
-                           for k, v in arrs.items()})
+    save_golden(os.path.join(OUT, name),                 # <name>.npz (+ <name>.partN.npz: every file under 1 MiB)
+                {k: (v.detach().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrs.items()})
     print('wrote', name, {k: tuple(np.asarray(v.detach() if torch.is_tensor(v) else v).shape)
                           for k, v in arrs.items()})
 

@@ -64,3 +64,73 @@ MAMC_CASES = {
     'all_distinct': (4, 1, 8, [0, 1, 2, 3]),
     'one_class': (3, 2, 8, [6, 6, 6]),
 }
+
+
+# ---------------------------------------------------------------- golden files under the 1 MiB limit of a committed file
+GOLDEN_PART_BYTES = 900 << 10
+
+
+class Golden(dict):
+    """The arrays of one golden, by key, in the order they were saved; `.files` as on numpy's NpzFile."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def _npz_bytes(arrays):
+    import io
+    b = io.BytesIO()
+    np.savez_compressed(b, **arrays)
+    return b.getvalue()
+
+
+def save_golden(base, arrays):
+    """Write `arrays` (name -> numpy array) as <base>.npz and, when one file would pass GOLDEN_PART_BYTES, further
+    <base>.part1.npz, <base>.part2.npz, ...  An array too large for one file is stored as slices along its first axis under
+    `<name>@0`, `<name>@1`, ...  load_golden(base) puts the arrays back together, key order included."""
+    import math
+    items = []
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        n = len(_npz_bytes({k: v}))
+        if n > GOLDEN_PART_BYTES and v.ndim >= 1 and v.shape[0] > 1:
+            pieces = np.array_split(v, min(v.shape[0], math.ceil(2 * n / GOLDEN_PART_BYTES)))
+            items += [(f'{k}@{i}', p) for i, p in enumerate(pieces)]
+        else:
+            items.append((k, v))
+    parts, cur = [], {}
+    for k, v in items:
+        if cur and len(_npz_bytes({**cur, k: v})) > GOLDEN_PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = v
+    parts.append(cur)
+    paths = [base + '.npz'] + [f'{base}.part{i}.npz' for i in range(1, len(parts))]
+    for path, part in zip(paths, parts):
+        with open(path, 'wb') as f:
+            f.write(_npz_bytes(part))
+    return paths
+
+
+def load_golden(base):
+    """<base>.npz and its <base>.partN.npz files (save_golden) as one Golden."""
+    import os
+    import re
+    out, paths, i = Golden(), [base + '.npz'], 1
+    while os.path.exists(f'{base}.part{i}.npz'):
+        paths.append(f'{base}.part{i}.npz')
+        i += 1
+    pieces = {}
+    for path in paths:
+        with np.load(path) as z:
+            for k in z.files:
+                m = re.fullmatch(r'(.+)@(\d+)', k)
+                if m:
+                    pieces.setdefault(m.group(1), []).append((int(m.group(2)), z[k]))
+                    out.setdefault(m.group(1), None)
+                else:
+                    out[k] = z[k]
+    for k, ps in pieces.items():
+        out[k] = np.concatenate([p for _, p in sorted(ps, key=lambda t: t[0])])
+    return out

@@ -101,3 +101,41 @@ def test_fractions_are_priced_on_executed_work_and_never_exceed_one():
     assert pad['frac'] == pytest.approx(6.711e9 / 72.4e-6 / 157.3e12, rel=1e-3)
     hbm = bench.roof_row('rank1', 10.7, 0.0, 51.4e6)
     assert hbm['bound'] == 'hbm' and hbm['unit'] == 'GB/s' and 0 < hbm['frac'] < 1
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'd'])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == 'd'
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float32_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: loss, every output tensor and every parameter as float32 .npy; arrays past the cap are the same
+    seeded sample of their elements in every run, and the whole dump stays under DUMP_MAX_BYTES."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 1 << 20)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(300, 1000), torch.nn.Linear(1000, 5))
+    out = (model(torch.randn(3, 300)), [torch.ones(2, dtype=torch.int64)])
+    loss = out[0].sum()
+    sizes = []
+    for d in ('a', 'b'):
+        sizes.append(bench.dump_outputs(str(tmp_path / d), loss, out, model))
+    assert sizes[0] == sizes[1] <= 1 << 20
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == sorted(['loss.npy', 'output.0.npy', 'output.1.0.npy', 'param.0.weight.npy', 'param.0.bias.npy',
+                            'param.1.weight.npy', 'param.1.bias.npy'])
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+    assert np.load(tmp_path / 'a' / 'loss.npy')[0] == pytest.approx(float(loss.detach()))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'output.0.npy'), out[0].detach().numpy())
+    w = np.load(tmp_path / 'a' / 'param.0.weight.npy')                # 300000 elements: sampled
+    assert w.ndim == 1 and w.size < 300000 and np.isin(w, model[0].weight.detach().numpy().ravel()).all()

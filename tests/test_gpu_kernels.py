@@ -32,7 +32,9 @@ def F():
 
 def _golden(name):
     import os
-    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', name + '.npz'))
+
+    from inputs import load_golden
+    return load_golden(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', name))
 
 
 def _fill_batches(c):

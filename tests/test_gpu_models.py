@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from inputs import rs_randn, seeded_init, sub
+from inputs import load_golden, rs_randn, seeded_init, sub
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), 'golden')
@@ -16,7 +16,7 @@ DEV = 'cuda'
 
 
 def load(name):
-    return np.load(os.path.join(G, name + '.npz'))
+    return load_golden(os.path.join(G, name))
 
 
 def t(a):
@@ -522,9 +522,9 @@ def test_rccl_path_executes_on_one_gpu(tmp_path):
 
 @pytest.mark.parametrize('world', [2, 8])
 def test_bench_spawns_its_own_ranks(tmp_path, world):
-    """`python bench.py --gpus N` (the driver's invocation shape, no torchrun around it) re-executes itself with one
-    process per rank - 2, and 8 as on the scaling node; here all ranks share the box's single GPU over gloo.  Rank 0 prints
-    the one JSON line, which carries the bucket timeline without being asked (N > 1)."""
+    """`python bench.py --gpus N` (the driver's invocation shape, no torchrun around it) runs itself with one
+    process per rank - 2, and 8 as on the scaling node; here all ranks share the one GPU over gloo.  Rank 0 prints
+    the one JSON line, which with --full carries the bucket timeline without being asked (N > 1)."""
     import json
     import subprocess
     import sys
@@ -532,7 +532,7 @@ def test_bench_spawns_its_own_ranks(tmp_path, world):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     env['HAWKEYE_BENCH_DETAIL'] = str(tmp_path / 'bench_detail.json')
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--share-gpu', '--backend', 'gloo',
-                        '--steps', '2', '--warmup', '1', '--batch', '2', '--image', '64'],
+                        '--steps', '2', '--warmup', '1', '--batch', '2', '--image', '64', '--full'],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -657,6 +657,32 @@ def test_bench_line_is_last_on_stdout_with_rccl(tmp_path):
         if rccl_log == '1':
             assert 'RCCL' in (out['ddp']['rccl']['version'] or ''), out['ddp']
             print('[bench --force-pg] ddp.rccl =', out['ddp']['rccl'])
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run (no --full): the line has the headline keys and nothing measured beside it, `steps` is what
+    was asked for, and --dump-outputs writes the last timed step's loss, logits and updated parameters as float32 .npy."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    env['HAWKEYE_BENCH_DETAIL'] = str(tmp_path / 'bench_detail.json')
+    d = tmp_path / 'dump'
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--batch', '2', '--image', '64', '--dump-outputs', str(d)],
+                       capture_output=True, text=True, timeout=900, env=env, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(p.stdout.rstrip().splitlines()[-1])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0 and out['value'] > 0
+    assert out['unit'] == 'images/sec' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert 'roofline' not in out and 'cpu_baseline' not in out and not os.path.exists(env['HAWKEYE_BENCH_DETAIL'])
+    loss, logits = np.load(d / 'loss.npy'), np.load(d / 'output.npy')
+    assert loss.dtype == logits.dtype == np.float32 and logits.shape == (2, 200) and np.isfinite(loss).all()
+    w = np.load(d / 'param.classifier.weight.npy')
+    assert w.dtype == np.float32 and w.ndim == 1 and 0 < w.size < 200 * 512 * 512 and np.isfinite(w).all()
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
 
 
 def test_trainer_runs_one_synthetic_epoch(tmp_path):

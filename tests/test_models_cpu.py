@@ -109,34 +109,35 @@ def test_forward_on_cpu_fails_loudly():
         m(torch.randn(1, 3, 64, 64))
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/configs'), reason='reference checkout not present')
+# the reference's configs/*.yaml, unchanged (settings only): tests/golden/reference_configs
+REF_CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_configs')
+
+
 def test_reference_yaml_configs_load_unchanged():
     """Every yaml of the reference loads through the yacs-compatible CfgNode (config.py:13-17 semantics)."""
     import glob
     from hawkeye_amd.config import load_config
-    files = sorted(glob.glob('/root/reference/configs/*.yaml'))
+    files = sorted(glob.glob(os.path.join(REF_CONFIGS, '*.yaml')))
     assert len(files) >= 20
     for f in files:
         cfg = load_config(f)
         assert cfg.is_frozen() and 'name' in cfg.model and 'experiment' in cfg
-    cfg = load_config('/root/reference/configs/BCNN_S2.yaml')
+    cfg = load_config(os.path.join(REF_CONFIGS, 'BCNN_S2.yaml'))
     assert cfg.model.stage == 2 and cfg.dataset.transformer.image_size == 448 and cfg.experiment.cuda == [0]
 
 
 @pytest.mark.parametrize('name', ['Baseline', 'BCNN_S1', 'BCNN_S2', 'CBCNN_S2', 'MPN', 'APCNN'])
 def test_in_repo_yaml_configs(name, monkeypatch):
     """The BASELINE configs (and the default configs/Baseline.yaml that setup_config falls back to) ship with the repo:
-    the GPU box has no /root/reference.  Each loads, names a registered plugin that constructs from its model node,
-    and - where the reference checkout exists - parses to exactly the reference's tree."""
+    the reference is not part of the repository.  Each loads, names a registered plugin that constructs from its model
+    node, and parses to exactly the reference's tree (its yaml, kept under tests/golden/reference_configs)."""
     from hawkeye_amd.config import load_config, setup_config
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cfg = load_config(os.path.join(root, 'configs', name + '.yaml'))
     assert cfg.is_frozen()
     model = MODEL.get(cfg.model.name)(cfg.model)
     assert sum(p.numel() for p in model.parameters()) > 1e6
-    ref = f'/root/reference/configs/{name}.yaml'
-    if os.path.exists(ref):
-        assert cfg.to_dict() == load_config(ref).to_dict()
+    assert cfg.to_dict() == load_config(os.path.join(REF_CONFIGS, name + '.yaml')).to_dict()
     if name == 'Baseline':
         monkeypatch.chdir(root)
         assert setup_config([]).to_dict() == cfg.to_dict()
