@@ -56,10 +56,6 @@ SIGNATURES = {
     'hk_cbp_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
     'hk_cbp_fwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
     'hk_cbp_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
-    'hk_cbp_bin_matrix': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
-    'hk_cbp_unbin_matrix': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
-    'hk_cbp_loc_fwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
-    'hk_cbp_loc_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     'hk_trunk_ws_bytes': (c_sz, [c_i]),
     'hk_bias_relu_fwd': (c_i, [c_f, c_f, c_f, c_ll, c_i, c_f]),
     'hk_bias_relu_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_f, c_sz, c_f]),

@@ -34,13 +34,20 @@ int cbp_fast_bwd_fused(const float* x, const int* h1, const int* h2, const float
                        hipStream_t st);
 static inline bool force_generic() { return tuning().bcnn_generic == 1; }   // A/B lever (hk_tuning_set)
 
-struct CbpPlan {  // device-side view of the plan blob
-    const int* h1;
-    const int* h2;
+// Device-side views of a plan blob.  Behind a 16-byte header, every blob starts with the same head - the hashes, the
+// signs and the CSR table bin -> (i * C2 + j, sign) of a C1 x C2 cross Gram - which is all the two-input kernels read.
+// hk_cbp_rect_plan_build writes the head alone; hk_cbp_plan_build writes it with C1 = C2 = C and appends what only the
+// one-input route (hk_cbp_fwd / bwd) needs.
+struct CbpHead {
+    const int* h1;       // [C1]
+    const int* h2;       // [C2]
     const float* s1;
     const float* s2;
     const int* off;      // [D+1]
-    const unsigned* ent; // [C*C]  bit31 = negative sign, low bits = i*C + j
+    const unsigned* ent; // [C1*C2]  bit31 = negative sign, low bits = i*C2 + j
+};
+
+struct CbpPlan : CbpHead {  // a hk_cbp_plan_build blob
     // inverse of h2 over its NON-EMPTY bins (row-sketch kernel): slot t holds bin nzb[t] and the channels
     // nzj[nzo[t] .. nzo[t+1]) hashed there (bit31 = negative s2)
     const int* nzb;      // [C]
@@ -52,6 +59,23 @@ struct CbpPlan {  // device-side view of the plan blob
 };
 
 __host__ __device__ inline size_t cbp_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// header + head: the whole blob of hk_cbp_rect_plan_build, the start of a hk_cbp_plan_build one (C1 = C2 = C)
+static inline size_t cbp_rect_bytes(int C1, int C2, int D) {
+    return 16 + 2 * cbp_align((size_t)C1 * 4) + 2 * cbp_align((size_t)C2 * 4) + cbp_align((size_t)(D + 1) * 4) +
+           cbp_align((size_t)C1 * C2 * 4);
+}
+static inline CbpHead cbp_rect_view(const void* plan, int C1, int C2, int D) {
+    const char* p = (const char*)plan + 16;
+    CbpHead v;
+    v.h1 = (const int*)p;            p += cbp_align((size_t)C1 * 4);
+    v.h2 = (const int*)p;            p += cbp_align((size_t)C2 * 4);
+    v.s1 = (const float*)p;          p += cbp_align((size_t)C1 * 4);
+    v.s2 = (const float*)p;          p += cbp_align((size_t)C2 * 4);
+    v.off = (const int*)p;           p += cbp_align((size_t)(D + 1) * 4);
+    v.ent = (const unsigned*)p;
+    return v;
+}
 // the blob carries the tile lists of the fused forward for every shape that kernel covers (whether THESE hashes allow
 // it is decided at build time and recorded in the word BEHIND the lists and in the host-side directory below:
 // hk_cbp_plan_build)
@@ -76,14 +100,9 @@ static inline int plan_fused_ok(const void* plan) {          // 0 no lists, 1 li
 }
 
 static inline CbpPlan cbp_view(const void* plan, int C, int D) {
-    const char* p = (const char*)plan + 16;
     CbpPlan v;
-    v.h1 = (const int*)p;            p += cbp_align((size_t)C * 4);
-    v.h2 = (const int*)p;            p += cbp_align((size_t)C * 4);
-    v.s1 = (const float*)p;          p += cbp_align((size_t)C * 4);
-    v.s2 = (const float*)p;          p += cbp_align((size_t)C * 4);
-    v.off = (const int*)p;           p += cbp_align((size_t)(D + 1) * 4);
-    v.ent = (const unsigned*)p;      p += cbp_align((size_t)C * C * 4);
+    static_cast<CbpHead&>(v) = cbp_rect_view(plan, C, C, D);
+    const char* p = (const char*)plan + cbp_rect_bytes(C, C, D);
     v.nzb = (const int*)p;           p += cbp_align((size_t)C * 4);
     v.nzo = (const int*)p;           p += cbp_align((size_t)(C + 1) * 4);
     v.nzj = (const unsigned*)p;          p += cbp_align((size_t)C * 4);
@@ -595,8 +614,9 @@ struct LdCbpDG {
 // CBCNN never takes (CBCNN.py:96-102 two DIFFERENT inputs; :127-130 sum_pool = False) - same count-sketch identity:
 //   two inputs:       c[b,k]   = sum_{(i,j) -> k} s1_i s2_j (X1 X2^T)[b,i,j]          a binning of the CROSS Gram
 //   per location:     c[b,p,k] = sum_{(i,j) -> k} s1_i s2_j x1[b,i,p] x2[b,j,p]       no sum over the map
-// Plain kernels (fixed summation orders, no atomics); the signed square root and F.normalize behind them are left to
-// the caller (hawkeye_amd/model/methods/CBCNN.py keeps the reference's own two lines for them).
+// Plain kernels (fixed summation orders, no atomics) over the head of a plan blob (CbpHead): any C1 x C2, and a
+// hk_cbp_plan_build blob with C1 = C2 = C.  The signed square root and F.normalize behind them are left to the caller
+// (hawkeye_amd/model/methods/CBCNN.py keeps the reference's own two lines for them).
 
 // dG[b,i,j] = s1_i s2_j dc[b, (h1_i + h2_j) mod D]        dG [B, C1, C2]
 __global__ __launch_bounds__(256) void cbp_unbin_kernel(const float* __restrict__ dc, const int* __restrict__ h1,
@@ -684,81 +704,43 @@ __global__ __launch_bounds__(256) void cbp_loc_bwd_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// input_dim1 != input_dim2 (CompactBilinearPooling(C1, C2, D), CBCNN.py:68-94): the same identity over a C1 x C2 cross
-// Gram.  A plan of its own - hashes, signs and the CSR table bin -> (i * C2 + j, sign) - and the plain kernels above; the
-// fused one-launch forms (hk_cbp_fwd / bwd) are for the square one-input case Hawkeye's CBCNN builds.
-struct CbpRectPlan {
-    const int* h1;       // [C1]
-    const int* h2;       // [C2]
-    const float* s1;
-    const float* s2;
-    const int* off;      // [D+1]
-    const unsigned* ent; // [C1*C2]
-};
-static inline size_t cbp_rect_bytes(int C1, int C2, int D) {
-    return 16 + 2 * cbp_align((size_t)C1 * 4) + 2 * cbp_align((size_t)C2 * 4) + cbp_align((size_t)(D + 1) * 4) +
-           cbp_align((size_t)C1 * C2 * 4);
+// Plan building (host).  The head of a blob - hashes, signs and the CSR table bin -> (i * C2 + j, sign) - written once for
+// both builders, at the offsets cbp_rect_view reads: (i, j) ascending inside each bin, the kernels' fixed summation order.
+static void cbp_fill_head(char* blob, const int32_t* h1, const float* s1, int C1, const int32_t* h2, const float* s2, int C2,
+                          int D) {
+    const CbpHead v = cbp_rect_view(blob, C1, C2, D);
+    memcpy((void*)v.h1, h1, (size_t)C1 * 4);
+    memcpy((void*)v.h2, h2, (size_t)C2 * 4);
+    memcpy((void*)v.s1, s1, (size_t)C1 * 4);
+    memcpy((void*)v.s2, s2, (size_t)C2 * 4);
+    int* off = const_cast<int*>(v.off);
+    unsigned* ent = const_cast<unsigned*>(v.ent);
+    std::vector<int> cnt(D, 0);
+    for (int i = 0; i < C1; ++i)
+        for (int j = 0; j < C2; ++j) cnt[(h1[i] + h2[j]) % D]++;
+    off[0] = 0;
+    for (int k = 0; k < D; ++k) off[k + 1] = off[k] + cnt[k];
+    std::vector<int> cur(off, off + D);
+    for (int i = 0; i < C1; ++i)
+        for (int j = 0; j < C2; ++j) {
+            const int k = (h1[i] + h2[j]) % D;
+            const unsigned neg = (s1[i] * s2[j] < 0.f) ? 0x80000000u : 0u;
+            ent[cur[k]++] = neg | (unsigned)(i * C2 + j);
+        }
 }
-static inline CbpRectPlan cbp_rect_view(const void* plan, int C1, int C2, int D) {
-    const char* p = (const char*)plan + 16;
-    CbpRectPlan v;
-    v.h1 = (const int*)p;            p += cbp_align((size_t)C1 * 4);
-    v.h2 = (const int*)p;            p += cbp_align((size_t)C2 * 4);
-    v.s1 = (const float*)p;          p += cbp_align((size_t)C1 * 4);
-    v.s2 = (const float*)p;          p += cbp_align((size_t)C2 * 4);
-    v.off = (const int*)p;           p += cbp_align((size_t)(D + 1) * 4);
-    v.ent = (const unsigned*)p;
-    return v;
+
+static int cbp_upload(void* plan, const std::vector<char>& blob, hk_stream_t stream) {
+    hipError_t e = hipMemcpyAsync(plan, blob.data(), blob.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    e = hipStreamSynchronize((hipStream_t)stream);   // one-time setup: the host blob dies at return
+    return e == hipSuccess ? HK_OK : (int)e;
 }
 
 }  // namespace hk
 
 using namespace hk;
 
-extern "C" int hk_cbp_bin_matrix(const float* G, const void* plan, float* c_raw, int B, int C, int D, hk_stream_t stream) {
-    if (!G || !plan || !c_raw || B <= 0 || C <= 0 || D <= 0) return HK_ERR_BAD_ARG;
-    if (B > 65535) return HK_ERR_UNSUPPORTED;
-    const CbpPlan pl = cbp_view(plan, C, D);
-    hipLaunchKernelGGL(cbp_bin_kernel, dim3((D + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, G, pl.off, pl.ent, c_raw, C * C, D);
-    HK_LAUNCH_CHECK();
-    return HK_OK;
-}
-
-extern "C" int hk_cbp_unbin_matrix(const float* dc, const void* plan, float* dG, int B, int C, int D, hk_stream_t stream) {
-    if (!dc || !plan || !dG || B <= 0 || C <= 0 || D <= 0) return HK_ERR_BAD_ARG;
-    if (B > 65535 || C > 65535) return HK_ERR_UNSUPPORTED;
-    const CbpPlan pl = cbp_view(plan, C, D);
-    hipLaunchKernelGGL(cbp_unbin_kernel, dim3((C + 255) / 256, C, B), dim3(256), 0, (hipStream_t)stream, dc, pl.h1, pl.h2, pl.s1,
-                       pl.s2, dG, C, C, D);
-    HK_LAUNCH_CHECK();
-    return HK_OK;
-}
-
-extern "C" int hk_cbp_loc_fwd(const float* x1, const float* x2, const void* plan, float* c, int B, int C, int HW, int D,
-                              hk_stream_t stream) {
-    if (!x1 || !x2 || !plan || !c || B <= 0 || C <= 0 || HW <= 0 || D <= 0) return HK_ERR_BAD_ARG;
-    if (C > 1024 || B > 65535) return HK_ERR_UNSUPPORTED;
-    const CbpPlan pl = cbp_view(plan, C, D);
-    hipLaunchKernelGGL(cbp_loc_fwd_kernel, dim3(HW, B), dim3(256), (size_t)2 * C * sizeof(float), (hipStream_t)stream, x1, x2,
-                       pl.off, pl.ent, c, C, C, HW, D);
-    HK_LAUNCH_CHECK();
-    return HK_OK;
-}
-
-extern "C" int hk_cbp_loc_bwd(const float* x1, const float* x2, const float* dc, const void* plan, float* dx1, float* dx2, int B,
-                              int C, int HW, int D, hk_stream_t stream) {
-    if (!x1 || !x2 || !dc || !plan || (!dx1 && !dx2) || B <= 0 || C <= 0 || HW <= 0 || D <= 0) return HK_ERR_BAD_ARG;
-    const size_t lds = ((size_t)D + 4 * (size_t)C) * sizeof(float);
-    if (lds > CBP_LOC_LDS_MAX || B > 65535) return HK_ERR_UNSUPPORTED;
-    HK_ALLOW_BIG_LDS(cbp_loc_bwd_kernel, lds);          // D = 16000, C = 512 is 72 KB: above the default 64 KB, well inside 160
-    const CbpPlan pl = cbp_view(plan, C, D);
-    hipLaunchKernelGGL(cbp_loc_bwd_kernel, dim3(HW, B), dim3(256), lds, (hipStream_t)stream, x1, x2, dc, pl.h1, pl.h2, pl.s1, pl.s2,
-                       dx1, dx2, C, C, HW, D);
-    HK_LAUNCH_CHECK();
-    return HK_OK;
-}
-
-// ------------------------------------------------------------------ input_dim1 != input_dim2
+// ------------------------------------------------------------------ two inputs, any widths (input_dim1 != input_dim2 too)
 extern "C" size_t hk_cbp_rect_plan_bytes(int C1, int C2, int D) {
     if (C1 <= 0 || C2 <= 0 || D <= 0) return 0;
     return cbp_rect_bytes(C1, C2, D);
@@ -775,35 +757,14 @@ extern "C" int hk_cbp_rect_plan_build(const int32_t* h1, const float* s1, int C1
     ((int*)blob.data())[0] = C1;
     ((int*)blob.data())[1] = C2;
     ((int*)blob.data())[2] = D;
-    char* p = blob.data() + 16;
-    memcpy(p, h1, (size_t)C1 * 4); p += cbp_align((size_t)C1 * 4);
-    memcpy(p, h2, (size_t)C2 * 4); p += cbp_align((size_t)C2 * 4);
-    memcpy(p, s1, (size_t)C1 * 4); p += cbp_align((size_t)C1 * 4);
-    memcpy(p, s2, (size_t)C2 * 4); p += cbp_align((size_t)C2 * 4);
-    int* off = (int*)p; p += cbp_align((size_t)(D + 1) * 4);
-    unsigned* ent = (unsigned*)p;
-    std::vector<int> cnt(D, 0);
-    for (int i = 0; i < C1; ++i)
-        for (int j = 0; j < C2; ++j) cnt[(h1[i] + h2[j]) % D]++;
-    off[0] = 0;
-    for (int k = 0; k < D; ++k) off[k + 1] = off[k] + cnt[k];
-    std::vector<int> cur(off, off + D);
-    for (int i = 0; i < C1; ++i)       // (i,j) ascending inside each bin: fixed summation order
-        for (int j = 0; j < C2; ++j) {
-            const int k = (h1[i] + h2[j]) % D;
-            const unsigned neg = (s1[i] * s2[j] < 0.f) ? 0x80000000u : 0u;
-            ent[cur[k]++] = neg | (unsigned)(i * C2 + j);
-        }
-    hipError_t e = hipMemcpyAsync(plan, blob.data(), blob.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    e = hipStreamSynchronize((hipStream_t)stream);   // one-time setup: the host blob dies at return
-    return e == hipSuccess ? HK_OK : (int)e;
+    cbp_fill_head(blob.data(), h1, s1, C1, h2, s2, C2, D);
+    return cbp_upload(plan, blob, stream);
 }
 
 extern "C" int hk_cbp_rect_bin_matrix(const float* G, const void* plan, float* c_raw, int B, int C1, int C2, int D, hk_stream_t stream) {
     if (!G || !plan || !c_raw || B <= 0 || C1 <= 0 || C2 <= 0 || D <= 0) return HK_ERR_BAD_ARG;
     if (B > 65535) return HK_ERR_UNSUPPORTED;
-    const CbpRectPlan pl = cbp_rect_view(plan, C1, C2, D);
+    const CbpHead pl = cbp_rect_view(plan, C1, C2, D);
     hipLaunchKernelGGL(cbp_bin_kernel, dim3((D + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, G, pl.off, pl.ent, c_raw, C1 * C2, D);
     HK_LAUNCH_CHECK();
     return HK_OK;
@@ -812,7 +773,7 @@ extern "C" int hk_cbp_rect_bin_matrix(const float* G, const void* plan, float* c
 extern "C" int hk_cbp_rect_unbin_matrix(const float* dc, const void* plan, float* dG, int B, int C1, int C2, int D, hk_stream_t stream) {
     if (!dc || !plan || !dG || B <= 0 || C1 <= 0 || C2 <= 0 || D <= 0) return HK_ERR_BAD_ARG;
     if (B > 65535 || C1 > 65535) return HK_ERR_UNSUPPORTED;
-    const CbpRectPlan pl = cbp_rect_view(plan, C1, C2, D);
+    const CbpHead pl = cbp_rect_view(plan, C1, C2, D);
     hipLaunchKernelGGL(cbp_unbin_kernel, dim3((C2 + 255) / 256, C1, B), dim3(256), 0, (hipStream_t)stream, dc, pl.h1, pl.h2, pl.s1,
                        pl.s2, dG, C1, C2, D);
     HK_LAUNCH_CHECK();
@@ -823,7 +784,7 @@ extern "C" int hk_cbp_rect_loc_fwd(const float* x1, const float* x2, const void*
                                    hk_stream_t stream) {
     if (!x1 || !x2 || !plan || !c || B <= 0 || C1 <= 0 || C2 <= 0 || HW <= 0 || D <= 0) return HK_ERR_BAD_ARG;
     if (C1 > 1024 || C2 > 1024 || B > 65535) return HK_ERR_UNSUPPORTED;
-    const CbpRectPlan pl = cbp_rect_view(plan, C1, C2, D);
+    const CbpHead pl = cbp_rect_view(plan, C1, C2, D);
     hipLaunchKernelGGL(cbp_loc_fwd_kernel, dim3(HW, B), dim3(256), (size_t)(C1 + C2) * sizeof(float), (hipStream_t)stream, x1, x2,
                        pl.off, pl.ent, c, C1, C2, HW, D);
     HK_LAUNCH_CHECK();
@@ -835,23 +796,17 @@ extern "C" int hk_cbp_rect_loc_bwd(const float* x1, const float* x2, const float
     if (!x1 || !x2 || !dc || !plan || (!dx1 && !dx2) || B <= 0 || C1 <= 0 || C2 <= 0 || HW <= 0 || D <= 0) return HK_ERR_BAD_ARG;
     const size_t lds = ((size_t)D + 2 * ((size_t)C1 + (size_t)C2)) * sizeof(float);
     if (lds > CBP_LOC_LDS_MAX || B > 65535) return HK_ERR_UNSUPPORTED;
-    HK_ALLOW_BIG_LDS(cbp_loc_bwd_kernel, lds);
-    const CbpRectPlan pl = cbp_rect_view(plan, C1, C2, D);
+    HK_ALLOW_BIG_LDS(cbp_loc_bwd_kernel, lds);          // D = 16000, C1 = C2 = 512 is 72 KB: above the default 64 KB, well inside 160
+    const CbpHead pl = cbp_rect_view(plan, C1, C2, D);
     hipLaunchKernelGGL(cbp_loc_bwd_kernel, dim3(HW, B), dim3(256), lds, (hipStream_t)stream, x1, x2, dc, pl.h1, pl.h2, pl.s1, pl.s2,
                        dx1, dx2, C1, C2, HW, D);
     HK_LAUNCH_CHECK();
     return HK_OK;
 }
 
-namespace hk {
-}  // namespace hk
-
-using namespace hk;
-
 extern "C" size_t hk_cbp_plan_bytes(int C, int D) {
     const size_t nb = (size_t)(C / 64);
-    return 16 + 4 * cbp_align((size_t)C * 4) + cbp_align((size_t)(D + 1) * 4) + cbp_align((size_t)C * C * 4) +
-           cbp_align((size_t)C * 4) + cbp_align((size_t)(C + 1) * 4) + cbp_align((size_t)C * 4) +
+    return cbp_rect_bytes(C, C, D) + cbp_align((size_t)C * 4) + cbp_align((size_t)(C + 1) * 4) + cbp_align((size_t)C * 4) +
            (cbp_has_lists(C, D) ? nb * nb * CBF_LLEN * sizeof(unsigned) + 16 : 0);
 }
 
@@ -861,68 +816,48 @@ extern "C" int hk_cbp_plan_build(const int32_t* h1, const float* s1, const int32
     for (int i = 0; i < C; ++i)
         if (h1[i] < 0 || h1[i] >= D || h2[i] < 0 || h2[i] >= D) return HK_ERR_BAD_ARG;   // CBCNN.py:153
     std::vector<char> blob(hk_cbp_plan_bytes(C, D), 0);
-    int fused_ok = 0;
-    ((int*)blob.data())[0] = C;
-    ((int*)blob.data())[1] = D;
-    char* p = blob.data() + 16;
-    memcpy(p, h1, (size_t)C * 4); p += cbp_align((size_t)C * 4);
-    memcpy(p, h2, (size_t)C * 4); p += cbp_align((size_t)C * 4);
-    memcpy(p, s1, (size_t)C * 4); p += cbp_align((size_t)C * 4);
-    memcpy(p, s2, (size_t)C * 4); p += cbp_align((size_t)C * 4);
-    int* off = (int*)p; p += cbp_align((size_t)(D + 1) * 4);
-    unsigned* ent = (unsigned*)p;
-    std::vector<int> cnt(D, 0);
-    for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) cnt[(h1[i] + h2[j]) % D]++;
-    off[0] = 0;
-    for (int k = 0; k < D; ++k) off[k + 1] = off[k] + cnt[k];
-    std::vector<int> cur(off, off + D);
-    for (int i = 0; i < C; ++i)        // (i,j) ascending inside each bin: fixed summation order
-        for (int j = 0; j < C; ++j) {
-            const int k = (h1[i] + h2[j]) % D;
-            const unsigned neg = (s1[i] * s2[j] < 0.f) ? 0x80000000u : 0u;
-            ent[cur[k]++] = neg | (unsigned)(i * C + j);
-        }
+    int* hdr = (int*)blob.data();
+    hdr[0] = C;
+    hdr[1] = D;
+    cbp_fill_head(blob.data(), h1, s1, C, h2, s2, C, D);
+    const CbpPlan v = cbp_view(blob.data(), C, D);
     // inverse of h2 over its non-empty bins (row-sketch kernel), channels ascending inside a bin
-    {
-        int* nzb = (int*)((char*)ent + cbp_align((size_t)C * C * 4));
-        int* nzo = (int*)((char*)nzb + cbp_align((size_t)C * 4));
-        unsigned* nzj = (unsigned*)((char*)nzo + cbp_align((size_t)(C + 1) * 4));
-        std::vector<std::vector<int>> inv(D);
-        for (int j = 0; j < C; ++j) inv[h2[j]].push_back(j);
-        // slots ordered by channel count, descending (ties: bin ascending): the few bins that two or more channels hash
-        // to (~22 of ~490 at C = 512, D = 6000) all land in the first wave of the binning kernels; every other wave has
-        // exactly one channel per bin and takes the single-gather path of cbp_rowscatter_kernel
-        std::vector<int> order;
-        for (int mbin = 0; mbin < D; ++mbin)
-            if (!inv[mbin].empty()) order.push_back(mbin);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return inv[a].size() > inv[b].size(); });
-        int t = 0, e = 0;
-        nzo[0] = 0;
-        for (int mbin : order) {
-            nzb[t] = mbin;
-            for (int j : inv[mbin]) nzj[e++] = (unsigned)j | (s2[j] < 0.f ? 0x80000000u : 0u);
-            nzo[++t] = e;
-        }
-        ((int*)blob.data())[2] = t;
-        int emax = 0;
-        for (int mbin = 0; mbin < D; ++mbin) emax = (int)inv[mbin].size() > emax ? (int)inv[mbin].size() : emax;
-        ((int*)blob.data())[3] = emax;
-        // tile lists of the fused forward + one word behind them: 1 = these hashes allow it
-        if (cbp_has_lists(C, D)) {
-            unsigned* lists = (unsigned*)((char*)nzj + cbp_align((size_t)C * 4));
-            std::vector<unsigned> L;
-            const int ok = cbf_build_lists(h1, s1, h2, s2, C, D, L);
-            const size_t nw = (size_t)(C / 64) * (C / 64) * CBF_LLEN;
-            if (ok) memcpy(lists, L.data(), nw * sizeof(unsigned));
-            lists[nw] = (unsigned)ok;
-            fused_ok = ok;
-        }
+    int* nzb = const_cast<int*>(v.nzb);
+    int* nzo = const_cast<int*>(v.nzo);
+    unsigned* nzj = const_cast<unsigned*>(v.nzj);
+    std::vector<std::vector<int>> inv(D);
+    for (int j = 0; j < C; ++j) inv[h2[j]].push_back(j);
+    // slots ordered by channel count, descending (ties: bin ascending): the few bins that two or more channels hash
+    // to (~22 of ~490 at C = 512, D = 6000) all land in the first wave of the binning kernels; every other wave has
+    // exactly one channel per bin and takes the single-gather path of cbp_rowscatter_kernel
+    std::vector<int> order;
+    for (int mbin = 0; mbin < D; ++mbin)
+        if (!inv[mbin].empty()) order.push_back(mbin);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return inv[a].size() > inv[b].size(); });
+    int t = 0, e = 0;
+    nzo[0] = 0;
+    for (int mbin : order) {
+        nzb[t] = mbin;
+        for (int j : inv[mbin]) nzj[e++] = (unsigned)j | (s2[j] < 0.f ? 0x80000000u : 0u);
+        nzo[++t] = e;
     }
-    hipError_t e = hipMemcpyAsync(plan, blob.data(), blob.size(), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    e = hipStreamSynchronize((hipStream_t)stream);   // one-time setup: the host blob dies at return
-    if (e != hipSuccess) return (int)e;
+    hdr[2] = t;
+    int emax = 0;
+    for (int mbin = 0; mbin < D; ++mbin) emax = (int)inv[mbin].size() > emax ? (int)inv[mbin].size() : emax;
+    hdr[3] = emax;
+    // tile lists of the fused forward + one word behind them: 1 = these hashes allow it
+    int fused_ok = 0;
+    if (v.lists) {
+        unsigned* lists = const_cast<unsigned*>(v.lists);
+        std::vector<unsigned> L;
+        const int ok = cbf_build_lists(h1, s1, h2, s2, C, D, L);
+        const size_t nw = (size_t)(C / 64) * (C / 64) * CBF_LLEN;
+        if (ok) memcpy(lists, L.data(), nw * sizeof(unsigned));
+        lists[nw] = (unsigned)ok;
+        fused_ok = ok;
+    }
+    const int rc = cbp_upload(plan, blob, stream);
+    if (rc != HK_OK) return rc;
     plan_note(plan, fused_ok);
     return HK_OK;
 }

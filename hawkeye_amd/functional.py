@@ -275,23 +275,31 @@ def sketch_hashes(input_dim1, input_dim2, output_dim):
 
 
 class CbpPlan:
-    """Device-side CSR plan (bin -> signed Gram entries) built once per device."""
+    """Device-side CSR plan (bin -> signed entries of the C1 x C2 cross Gram) built once per device.  One width (C1 = C2):
+    the hk_cbp_plan_build blob the one-input route (compact_bilinear_pool) needs; two widths (CBCNN.py:68-94): the
+    hk_cbp_rect_plan_build blob.  The two-input forms (compact_bilinear_sketch) take either."""
 
     def __init__(self, h1, s1, h2, s2, output_dim, device):
         lib = _lib.load()
         assert h1.ndim == 1 and s1.ndim == 1 and len(h1) == len(s1)            # CBCNN.py:151-152
-        assert len(h1) == len(h2), 'the Gram route needs input_dim1 == input_dim2'
+        assert h2.ndim == 1 and s2.ndim == 1 and len(h2) == len(s2)
         assert np.all(h1 >= 0) and np.all(h1 < output_dim)                      # CBCNN.py:153
         assert np.all(h2 >= 0) and np.all(h2 < output_dim)
-        self.C, self.D, self.device = len(h1), int(output_dim), device
+        self.C1, self.C2, self.D, self.device = len(h1), len(h2), int(output_dim), device
         h1 = np.ascontiguousarray(h1, dtype=np.int32)
         h2 = np.ascontiguousarray(h2, dtype=np.int32)
         s1 = np.ascontiguousarray(s1, dtype=np.float32)
         s2 = np.ascontiguousarray(s2, dtype=np.float32)
-        self.blob = torch.empty(lib.hk_cbp_plan_bytes(self.C, self.D), dtype=torch.uint8, device=device)
-        with _on(device):
-            check(lib.hk_cbp_plan_build(h1.ctypes.data, s1.ctypes.data, h2.ctypes.data, s2.ctypes.data,
-                                        self.C, self.D, ptr(self.blob), stream()), 'hk_cbp_plan_build')
+        if self.C1 == self.C2:
+            self.blob = torch.empty(lib.hk_cbp_plan_bytes(self.C1, self.D), dtype=torch.uint8, device=device)
+            with _on(device):
+                check(lib.hk_cbp_plan_build(h1.ctypes.data, s1.ctypes.data, h2.ctypes.data, s2.ctypes.data,
+                                            self.C1, self.D, ptr(self.blob), stream()), 'hk_cbp_plan_build')
+        else:
+            self.blob = torch.empty(lib.hk_cbp_rect_plan_bytes(self.C1, self.C2, self.D), dtype=torch.uint8, device=device)
+            with _on(device):
+                check(lib.hk_cbp_rect_plan_build(h1.ctypes.data, s1.ctypes.data, self.C1, h2.ctypes.data, s2.ctypes.data,
+                                                 self.C2, self.D, ptr(self.blob), stream()), 'hk_cbp_rect_plan_build')
 
     def __del__(self):
         # the library keeps a host-side note per plan ADDRESS: forget it before torch can hand the memory to someone else
@@ -311,8 +319,8 @@ class _CompactBilinearPool(torch.autograd.Function):
         x = _f32c(x)
         b, c, h, w = x.shape
         hw, d = h * w, plan.D
-        if plan.C != c:
-            raise _lib.HawkeyeHipError(f'compact_bilinear_pool: the plan was built for {plan.C} channels, input has {c}')
+        if (plan.C1, plan.C2) != (c, c):
+            raise _lib.HawkeyeHipError(f'compact_bilinear_pool: the plan was built for {plan.C1} x {plan.C2} channels, input has {c}')
         y = torch.empty(b, d, dtype=torch.float32, device=x.device)
         c_raw = torch.empty(b, d, dtype=torch.float32, device=x.device)
         inv_norm = torch.empty(b, dtype=torch.float32, device=x.device)
@@ -349,109 +357,6 @@ def _bgemm_raw(lib, a, b, out, trans_a, trans_b, m, n, k, nb):
                            int(trans_b), ptr(out), n, m * n, m, n, k, nb, 1.0, 0.0, 0.0, stream()), 'hk_bgemm_f32')
 
 
-class _CbpCrossSum(torch.autograd.Function):
-    """Count sketch of the summed outer product of TWO different maps (CompactBilinearPooling.forward with bottom2 given,
-    CBCNN.py:96-130, before its signed sqrt): c[b,k] = sum_{(i,j) -> k} s1_i s2_j (X1 X2^T)[b,i,j] - the cross Gram on the
-    generic MFMA tiles (hk_bgemm_f32), the plan's CSR gather over it (hk_cbp_bin_matrix); backward: dG from dc
-    (hk_cbp_unbin_matrix), dX1 = dG X2, dX2 = dG^T X1."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, plan):
-        lib = _lib.load()
-        x1, x2 = _f32c(x1), _f32c(x2)
-        b, c, h, w = x1.shape
-        if tuple(x2.shape) != (b, c, h, w) or plan.C != c:
-            raise _lib.HawkeyeHipError(f'compact_bilinear_pool: inputs {tuple(x1.shape)} / {tuple(x2.shape)}, plan for {plan.C} channels')
-        hw, d = h * w, plan.D
-        g = torch.empty(b, c, c, dtype=torch.float32, device=x1.device)
-        _bgemm_raw(lib, x1.view(b, c, hw), x2.view(b, c, hw), g, False, True, c, c, hw, b)
-        c_raw = torch.empty(b, d, dtype=torch.float32, device=x1.device)
-        check(lib.hk_cbp_bin_matrix(ptr(g), ptr(plan.blob), ptr(c_raw), b, c, d, stream()), 'hk_cbp_bin_matrix')
-        ctx.plan = plan
-        ctx.save_for_backward(x1, x2)
-        return c_raw
-
-    @staticmethod
-    def backward(ctx, dc):
-        lib = _lib.load()
-        x1, x2 = ctx.saved_tensors
-        plan = ctx.plan
-        b, c, h, w = x1.shape
-        hw, d = h * w, plan.D
-        dc = _f32c(dc)
-        dg = torch.empty(b, c, c, dtype=torch.float32, device=x1.device)
-        check(lib.hk_cbp_unbin_matrix(ptr(dc), ptr(plan.blob), ptr(dg), b, c, d, stream()), 'hk_cbp_unbin_matrix')
-        dx1 = dx2 = None
-        if ctx.needs_input_grad[0]:
-            dx1 = torch.empty_like(x1)
-            _bgemm_raw(lib, dg, x2.view(b, c, hw), dx1.view(b, c, hw), False, False, c, hw, c, b)
-        if ctx.needs_input_grad[1]:
-            dx2 = torch.empty_like(x2)
-            _bgemm_raw(lib, dg, x1.view(b, c, hw), dx2.view(b, c, hw), True, False, c, hw, c, b)
-        return dx1, dx2, None
-
-
-def _loc_bwd_fits(ctx, c1, c2, d):
-    """hk_cbp_loc_bwd keeps dc[b,p,:], both channel columns and both hash tables of a location in LDS (144 KB of the CU's 160):
-    say so in the FORWARD of a pass that will need it, not in the middle of backward()."""
-    if any(ctx.needs_input_grad[:2]) and (d + 2 * (c1 + c2)) * 4 > 144 * 1024:
-        raise _lib.HawkeyeHipError(f'compact_bilinear_pool(sum_pool=False): the backward holds D + 2 (C1 + C2) = {d + 2 * (c1 + c2)} '
-                                   f'floats per location in LDS (limit {144 * 256}); run this shape under torch.no_grad() or reduce D')
-
-
-class _CbpPerLocation(torch.autograd.Function):
-    """The tensor sketch of every location on its own (CompactBilinearPooling.forward with sum_pool = False, CBCNN.py:117-128
-    before its signed sqrt): c[b,h,w,k] = sum_{(i,j) -> k} s1_i s2_j x1[b,i,h,w] x2[b,j,h,w]  ->  [B,H,W,D]."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, plan):
-        lib = _lib.load()
-        x1, x2 = _f32c(x1), _f32c(x2)
-        b, c, h, w = x1.shape
-        if tuple(x2.shape) != (b, c, h, w) or plan.C != c:
-            raise _lib.HawkeyeHipError(f'compact_bilinear_pool: inputs {tuple(x1.shape)} / {tuple(x2.shape)}, plan for {plan.C} channels')
-        _loc_bwd_fits(ctx, c, c, plan.D)
-        out = torch.empty(b, h, w, plan.D, dtype=torch.float32, device=x1.device)
-        check(lib.hk_cbp_loc_fwd(ptr(x1), ptr(x2), ptr(plan.blob), ptr(out), b, c, h * w, plan.D, stream()), 'hk_cbp_loc_fwd')
-        ctx.plan = plan
-        ctx.save_for_backward(x1, x2)
-        return out
-
-    @staticmethod
-    def backward(ctx, dc):
-        lib = _lib.load()
-        x1, x2 = ctx.saved_tensors
-        plan = ctx.plan
-        b, c, h, w = x1.shape
-        dc = _f32c(dc)
-        dx1 = torch.empty_like(x1) if ctx.needs_input_grad[0] else None
-        dx2 = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
-        check(lib.hk_cbp_loc_bwd(ptr(x1), ptr(x2), ptr(dc), ptr(plan.blob), ptr(dx1), ptr(dx2), b, c, h * w, plan.D, stream()),
-              'hk_cbp_loc_bwd')
-        return dx1, dx2, None
-
-
-class CbpRectPlan:
-    """Device-side plan for input_dim1 != input_dim2 (CompactBilinearPooling(C1, C2, D), CBCNN.py:68-94): hashes, signs and
-    the CSR table bin -> signed entries of the C1 x C2 cross Gram.  No host-side state in the library."""
-
-    def __init__(self, h1, s1, h2, s2, output_dim, device):
-        lib = _lib.load()
-        assert h1.ndim == 1 and s1.ndim == 1 and len(h1) == len(s1)            # CBCNN.py:151-152
-        assert h2.ndim == 1 and s2.ndim == 1 and len(h2) == len(s2)
-        assert np.all(h1 >= 0) and np.all(h1 < output_dim)                      # CBCNN.py:153
-        assert np.all(h2 >= 0) and np.all(h2 < output_dim)
-        self.C1, self.C2, self.D, self.device = len(h1), len(h2), int(output_dim), device
-        h1 = np.ascontiguousarray(h1, dtype=np.int32)
-        h2 = np.ascontiguousarray(h2, dtype=np.int32)
-        s1 = np.ascontiguousarray(s1, dtype=np.float32)
-        s2 = np.ascontiguousarray(s2, dtype=np.float32)
-        self.blob = torch.empty(lib.hk_cbp_rect_plan_bytes(self.C1, self.C2, self.D), dtype=torch.uint8, device=device)
-        with _on(device):
-            check(lib.hk_cbp_rect_plan_build(h1.ctypes.data, s1.ctypes.data, self.C1, h2.ctypes.data, s2.ctypes.data, self.C2,
-                                             self.D, ptr(self.blob), stream()), 'hk_cbp_rect_plan_build')
-
-
 def _rect_shapes(x1, x2, plan, what):
     b, c1, h, w = x1.shape
     if x2.shape[0] != b or tuple(x2.shape[2:]) != (h, w) or (c1, x2.shape[1]) != (plan.C1, plan.C2):
@@ -459,9 +364,11 @@ def _rect_shapes(x1, x2, plan, what):
     return b, c1, x2.shape[1], h, w
 
 
-class _CbpRectSum(torch.autograd.Function):
-    """_CbpCrossSum for two inputs of DIFFERENT widths: the C1 x C2 cross Gram on the generic MFMA tiles, the rect plan's
-    gather over it; backward dG from dc, dX1 = dG X2, dX2 = dG^T X1."""
+class _CbpCrossSum(torch.autograd.Function):
+    """Count sketch of the summed outer product of TWO different maps (CompactBilinearPooling.forward with bottom2 given,
+    CBCNN.py:96-130, before its signed sqrt): c[b,k] = sum_{(i,j) -> k} s1_i s2_j (X1 X2^T)[b,i,j] - the C1 x C2 cross Gram
+    on the generic MFMA tiles (hk_bgemm_f32), the plan's CSR gather over it (hk_cbp_rect_bin_matrix); backward: dG from dc
+    (hk_cbp_rect_unbin_matrix), dX1 = dG X2, dX2 = dG^T X1."""
 
     @staticmethod
     def forward(ctx, x1, x2, plan):
@@ -497,8 +404,17 @@ class _CbpRectSum(torch.autograd.Function):
         return dx1, dx2, None
 
 
-class _CbpRectPerLocation(torch.autograd.Function):
-    """_CbpPerLocation for two inputs of different widths (sum_pool = False)."""
+def _loc_bwd_fits(ctx, c1, c2, d):
+    """hk_cbp_rect_loc_bwd keeps dc[b,p,:], both channel columns and both hash tables of a location in LDS (144 KB of the CU's 160):
+    say so in the FORWARD of a pass that will need it, not in the middle of backward()."""
+    if any(ctx.needs_input_grad[:2]) and (d + 2 * (c1 + c2)) * 4 > 144 * 1024:
+        raise _lib.HawkeyeHipError(f'compact_bilinear_pool(sum_pool=False): the backward holds D + 2 (C1 + C2) = {d + 2 * (c1 + c2)} '
+                                   f'floats per location in LDS (limit {144 * 256}); run this shape under torch.no_grad() or reduce D')
+
+
+class _CbpPerLocation(torch.autograd.Function):
+    """The tensor sketch of every location on its own (CompactBilinearPooling.forward with sum_pool = False, CBCNN.py:117-128
+    before its signed sqrt): c[b,h,w,k] = sum_{(i,j) -> k} s1_i s2_j x1[b,i,h,w] x2[b,j,h,w]  ->  [B,H,W,D]."""
 
     @staticmethod
     def forward(ctx, x1, x2, plan):
@@ -529,9 +445,7 @@ class _CbpRectPerLocation(torch.autograd.Function):
 
 def compact_bilinear_sketch(x1, x2, plan, sum_pool=True):
     """The count sketch BEFORE the signed square root, for the forms Hawkeye's own CBCNN does not take: two different inputs
-    ([B,D]) or no sum over the map ([B,H,W,D]); x2 may be x1.  A CbpRectPlan (input_dim1 != input_dim2) takes the C1 x C2 forms."""
-    if isinstance(plan, CbpRectPlan):
-        return _CbpRectSum.apply(x1, x2, plan) if sum_pool else _CbpRectPerLocation.apply(x1, x2, plan)
+    ([B,D]) or no sum over the map ([B,H,W,D]); x2 may be x1.  Any widths C1, C2 of the plan."""
     return _CbpCrossSum.apply(x1, x2, plan) if sum_pool else _CbpPerLocation.apply(x1, x2, plan)
 
 

@@ -30,9 +30,8 @@ class CompactBilinearPooling(nn.Module):
     def _plan(self, device):
         key = (device.type, device.index)
         if key not in self._plans:
-            # two widths (CBCNN.py:68-94 sizes each sketch matrix by its own input_dim): the plan over the C1 x C2 cross Gram
-            make = HF.CbpPlan if self.input_dim1 == self.input_dim2 else HF.CbpRectPlan
-            self._plans[key] = make(self.rand_h_1, self.rand_s_1, self.rand_h_2, self.rand_s_2, self.output_dim, device)
+            # (CBCNN.py:68-94 sizes each sketch matrix by its own input_dim: the plan is over the C1 x C2 cross Gram)
+            self._plans[key] = HF.CbpPlan(self.rand_h_1, self.rand_s_1, self.rand_h_2, self.rand_s_2, self.output_dim, device)
         return self._plans[key]
 
     def __deepcopy__(self, memo):          # plans hold device blobs: rebuild lazily in the copy

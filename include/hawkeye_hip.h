@@ -231,29 +231,18 @@ int hk_cbp_bwd(const float* x, const void* plan, const float* y, const float* c_
                hk_stream_t stream);
 
 /* The two forms of CompactBilinearPooling.forward Hawkeye's own CBCNN never takes (it calls it with one input and
- * sum_pool = True, CBCNN.py:23,33): two DIFFERENT inputs (CBCNN.py:96-102) and sum_pool = False (:127-130).  Same identity:
- *   hk_cbp_bin_matrix    c_raw[b,k]  = sum_{(i,j) -> k} s1_i s2_j G[b,i,j]      for a given G [B,C,C] (the cross Gram X1 X2^T:
- *                                                                              hk_bgemm_f32) - the plan's CSR gather
- *   hk_cbp_unbin_matrix  dG[b,i,j]   = s1_i s2_j dc[b, (h1_i + h2_j) mod D]     its transpose (then dX1 = dG X2, dX2 = dG^T X1)
- *   hk_cbp_loc_fwd       c[b,p,k]    = sum_{(i,j) -> k} s1_i s2_j x1[b,i,p] x2[b,j,p]     c [B,HW,D], no sum over the map
- *   hk_cbp_loc_bwd       dx1, dx2 [B,C,HW] from dc [B,HW,D] (either output nullable)
- * The signed square root and F.normalize (CBCNN.py:132-133) are the caller's; C (= both input widths) <= 1024 for _loc_. */
-int hk_cbp_bin_matrix(const float* G, const void* plan, float* c_raw, int B, int C, int D, hk_stream_t stream);
-int hk_cbp_unbin_matrix(const float* dc, const void* plan, float* dG, int B, int C, int D, hk_stream_t stream);
-int hk_cbp_loc_fwd(const float* x1, const float* x2, const void* plan, float* c, int B, int C, int HW, int D,
-                   hk_stream_t stream);
-int hk_cbp_loc_bwd(const float* x1, const float* x2, const float* dc, const void* plan, float* dx1, float* dx2, int B,
-                   int C, int HW, int D, hk_stream_t stream);
-
-/* input_dim1 != input_dim2: CompactBilinearPooling(C1, C2, D) (model/methods/CBCNN.py:68-94 builds one sketch matrix per
- * input width; :104-105 asserts bottom1 has C1 and bottom2 C2 channels).  The same identity over the C1 x C2 cross Gram
- * G = X1 X2^T (hk_bgemm_f32):   c[b,k] = sum_{(i,j) : (h1[i] + h2[j]) mod D = k} s1[i] s2[j] G[b,i,j].
+ * sum_pool = True, CBCNN.py:23,33): two DIFFERENT inputs (CBCNN.py:96-102) and sum_pool = False (:127-130), for any widths
+ * C1, C2 (CompactBilinearPooling(C1, C2, D), CBCNN.py:68-94 builds one sketch matrix per input width; :104-105 asserts
+ * bottom1 has C1 and bottom2 C2 channels).  The same identity over the C1 x C2 cross Gram G = X1 X2^T (hk_bgemm_f32):
+ *   c[b,k] = sum_{(i,j) : (h1[i] + h2[j]) mod D = k} s1[i] s2[j] G[b,i,j].
  *   hk_cbp_rect_plan_build   hashes h1 [C1], h2 [C2] in [0,D), signs s1 [C1], s2 [C2] (HOST pointers) -> `plan` (DEVICE memory,
  *                            hk_cbp_rect_plan_bytes(C1, C2, D) bytes: the hashes, the signs and the CSR table bin -> (i*C2+j, sign))
  *   hk_cbp_rect_bin_matrix   G [B,C1,C2] -> c_raw [B,D]            hk_cbp_rect_unbin_matrix   dc [B,D] -> dG [B,C1,C2]
  *                            (then dX1 = dG X2, dX2 = dG^T X1)
  *   hk_cbp_rect_loc_fwd/bwd  sum_pool = False: x1 [B,C1,HW], x2 [B,C2,HW] <-> c [B,HW,D]   (C1, C2 <= 1024; either gradient nullable)
- * A rect plan holds no host-side state (nothing to destroy).  The signed square root and F.normalize stay the caller's. */
+ * The four kernels' entry points take a plan from either builder: a hk_cbp_plan_build blob starts with the same bytes
+ * (from offset 16 on) as the hk_cbp_rect_plan_build blob of its hashes, so pass it with C1 = C2 = C.  A rect plan holds no
+ * host-side state (nothing to destroy).  The signed square root and F.normalize stay the caller's. */
 size_t hk_cbp_rect_plan_bytes(int C1, int C2, int D);
 int hk_cbp_rect_plan_build(const int32_t* h1, const float* s1, int C1, const int32_t* h2, const float* s2, int C2, int D,
                            void* plan, hk_stream_t stream);

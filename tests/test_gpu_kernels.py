@@ -459,6 +459,26 @@ def test_cbp_row_scatter_binning(F, c, d, b, tune):
     assert rel(out['2'][0], y64) < 1e-5
 
 
+def test_cbp_square_plan_starts_with_the_rect_plan(F):
+    """The two-input entry points (hk_cbp_rect_*) take a hk_cbp_plan_build blob with C1 = C2 = C: behind the 16-byte
+    header it holds the hk_cbp_rect_plan_build blob of the same hashes byte for byte.  (512, 6000) and (128, 512) carry the
+    fused forward's tile lists, 200 is not a multiple of 64.  hk_cbp_plan_bytes is pinned: the one-input route's layout
+    behind the head stays as it is."""
+    from hawkeye_amd import _lib
+    lib = _lib.load()
+    ptr, stream = F.ptr, F.stream
+    dev = torch.device(DEV) if DEV != 'cuda' else torch.device('cuda', torch.cuda.current_device())
+    for c, d, nbytes in ((512, 6000, 2266624), (200, 1000, 169648), (128, 512, 144960)):
+        h1, s1, h2, s2 = F.sketch_hashes(c, c, d)
+        square = F.CbpPlan(h1, s1, h2, s2, d, dev)
+        n = lib.hk_cbp_rect_plan_bytes(c, c, d)
+        rect = torch.zeros(n, dtype=torch.uint8, device=dev)
+        assert lib.hk_cbp_rect_plan_build(h1.ctypes.data, s1.ctypes.data, c, h2.ctypes.data, s2.ctypes.data, c, d, ptr(rect),
+                                          stream()) == 0
+        assert lib.hk_cbp_plan_bytes(c, d) == nbytes == square.blob.numel(), (c, d)
+        assert torch.equal(rect[16:].cpu(), square.blob[16:n].cpu()), (c, d)
+
+
 @pytest.mark.parametrize('channels_last', [False, True])
 def test_image_finalize_bit_exact(F, channels_last):
     """hk_image_finalize vs the CPU order of operations (u8 / 255 - mean) / std + erase: bit-identical,
