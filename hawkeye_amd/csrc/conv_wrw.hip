@@ -1,0 +1,242 @@
+// Weight gradient of the trunk's 3 x 3 convolutions with 64 input channels (model/backbone/vgg.py:24-57: conv1_2, 64 -> 64 at
+// 448 x 448, and conv2_1, 64 -> 128 at 224 x 224; stride 1, padding 1, fp32, channels_last):
+//   dW[o][kh][kw][ci] = sum over pixels of dy[pix][o] x[pix + (kh - 1, kw - 1)][ci]
+// - a GEMM with M = Cout, N = 9 * 64 = 576 and K = N H W pixels (12.8 M at the metric shape).  The library runs these two
+// layers on a 64 x 64 tile with one 32 x 32 MFMA block per wave (an LDS operand fetch for almost every MFMA) and splits K
+// with float atomics behind a zero-fill: 112 - 122 TF/s where its other weight gradients reach 131
+// (profiles/r6_step_BCNN_kernel_stats.csv).  Here a workgroup keeps a WHOLE 64 x 576 result in its accumulators (four
+// waves x nine 32 x 32 blocks = 144 registers per lane) over all the pixels it is given, so that the matrix pipe is the only
+// thing that is busy: per pixel pair a wave reads one A and nine B values from LDS for nine MFMAs.
+//
+//   NHWC is the MFMA's own operand layout: v_mfma_f32_32x32x2_f32 wants A[i = lane % 32][k = lane / 32] and
+//   B[k = lane / 32][j = lane % 32]; with k = the pixel of a pair, i = output channel, j = input channel, a lane's A value is
+//   dy[pix + lane / 32][o0 + lane % 32] and its B value x[pix + shift + lane / 32][c0 + lane % 32]: 32 consecutive floats per
+//   half wave, conflict-free ds_read_b32 at any pitch.
+//
+//   job      = (image, strip of 32 columns, block of rows); a workgroup owns a fixed, contiguous list of jobs
+//   row step = one image row of the strip: the dy segment (32 pixels x 64 channels of the workgroup's Cout slice) and the x
+//              segment of the row below (34 pixels with the column halo x 64) come in through registers while the MFMAs of the
+//              current row run - the three x rows a step needs stay in a four-slot LDS ring, dy is double-buffered; one barrier
+//              per step (144 MFMAs per wave)
+//   borders  = rows -1 and H, columns -1 and W, the pixels past a ragged last strip: zeros in LDS (the load is made from a
+//              clamped, in-bounds address and replaced) - nothing outside the two tensors is read, rows of the neighbouring
+//              image are never used
+//   result   = every workgroup writes its 64 x 576 partial; partial_sum_kernel adds the partials of an element in a fixed order
+//              (no atomics, no zero-fill: the same input gives the same bits)
+#include "hk_common.h"
+#include "hk_partial_sum.h"
+#include "../../include/hawkeye_hip.h"
+
+namespace hk {
+
+constexpr int WRW_CI = 64;                               // input channels
+constexpr int WRW_OT = 64;                               // output channels per workgroup
+constexpr int WRW_SW = 32;                               // strip width (pixels per row step)
+constexpr int WRW_XROW = (WRW_SW + 2) * WRW_CI;          // floats of an x row segment (column halo on both sides)
+constexpr int WRW_DYROW = WRW_SW * WRW_OT;               // floats of a dy row segment
+constexpr int WRW_XF4 = WRW_XROW / 4;                    // 544 float4
+constexpr int WRW_LDS = 4 * WRW_XROW + 2 * WRW_DYROW;    // 12800 floats = 50 KB
+constexpr int WRW_MIN_ROWS = 4;                          // a row block is at least this high (each block re-reads two halo rows)
+constexpr int WRW_MAX_WG = 512;                          // workgroups per Cout slice, at most (= partial results in the workspace)
+
+// this thread's float4 loads of one row segment: where they come from (clamped into the tensor) and whether they count
+struct WrwStage {
+    long long xoff[3], doff[2];
+    bool xok[3], dok[2];
+};
+
+// The loads are untracked (HK_LOAD16_ASYNC: they stay where they are written, in front of the step's MFMAs - left to the compiler,
+// they end up behind the MFMAs, next to the LDS stores that use them), unconditional (clamped, in-bounds addresses), and waited for
+// by wrw_loads_landed() behind the MFMAs; the zeros of the borders are put in on the way to LDS
+__device__ __forceinline__ bool wrw_load_x(const float* __restrict__ xi, const WrwStage& st, int r, int H, int W, f32x4 (&v)[3]) {
+    const bool rok = r >= 0 && r < H;
+    const float* row = xi + (long long)(r < 0 ? 0 : (r < H ? r : H - 1)) * W * WRW_CI;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) HK_LOAD16_ASYNC(v[u], row + st.xoff[u]);
+    return rok;
+}
+__device__ __forceinline__ void wrw_load_dy(const float* __restrict__ dyi, const WrwStage& st, int h, int H, int W, int Cout, f32x4 (&v)[2]) {
+    const float* row = dyi + (long long)(h < H ? h : H - 1) * W * Cout;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) HK_LOAD16_ASYNC(v[u], row + st.doff[u]);
+}
+__device__ __forceinline__ void wrw_loads_landed(f32x4 (&vx)[3], f32x4 (&vd)[2]) {
+    __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
+#pragma unroll
+    for (int u = 0; u < 3; ++u) HK_PIN_LOADED(vx[u]);    // (no use of the registers moves in front of the wait)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) HK_PIN_LOADED(vd[u]);
+}
+__device__ __forceinline__ void wrw_store_x(float* __restrict__ xs, int slot, const WrwStage& st, bool rok, const f32x4 (&v)[3]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4* d = reinterpret_cast<f32x4*>(xs + slot * WRW_XROW) + threadIdx.x;
+    d[0] = (rok && st.xok[0]) ? v[0] : zero;
+    d[256] = (rok && st.xok[1]) ? v[1] : zero;
+    if (threadIdx.x + 512 < WRW_XF4) d[512] = (rok && st.xok[2]) ? v[2] : zero;
+}
+__device__ __forceinline__ void wrw_store_dy(float* __restrict__ ds, int buf, const WrwStage& st, const f32x4 (&v)[2]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4* d = reinterpret_cast<f32x4*>(ds + buf * WRW_DYROW) + threadIdx.x;
+    d[0] = st.dok[0] ? v[0] : zero;
+    d[256] = st.dok[1] ? v[1] : zero;
+}
+
+// dy [N][H][W][Cout], x [N][H][W][64] -> part [gridDim.x][Cout][9][64].  grid (workgroups per slice, Cout / 64).
+// job j = ((n nrb + rb) nstrips + strip): rows [rb rpb, min(H, (rb + 1) rpb)), columns [32 strip, 32 strip + 32)
+__global__ __launch_bounds__(256, 2) void conv3x3_wrw_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                          float* __restrict__ part, int H, int W, int Cout, int nstrips, int nrb,
+                                                          int rpb, int njobs) {
+    __shared__ __attribute__((aligned(16))) float lds[WRW_LDS];
+    float* xs = lds;                                     // ring of four x row segments: [slot][34 pixels][64]
+    float* ds = lds + 4 * WRW_XROW;                      // two dy row segments: [buf][32 pixels][64]
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int oh = wave >> 1, ch = wave & 1;            // this wave's 32 output channels x 32 input channels, all nine taps
+    const int slice = blockIdx.y;
+    const int jb = (int)((long long)blockIdx.x * njobs / gridDim.x), je = (int)((long long)(blockIdx.x + 1) * njobs / gridDim.x);
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+
+    const int aoff = hf * WRW_OT + oh * 32 + l31;        // + 64 (pixel of the strip): this lane's A value
+    const int boff = hf * WRW_CI + ch * 32 + l31;        // + 64 (pixel of the strip + kw): this lane's B value
+
+    for (int j = jb; j < je; ++j) {
+        const int strip = j % nstrips, jr = j / nstrips;
+        const int rb = jr % nrb;
+        const long long n = jr / nrb;
+        const int c0 = strip * WRW_SW, r0 = rb * rpb;
+        const int nrows = (r0 + rpb < H ? r0 + rpb : H) - r0;
+        const float* xi = x + n * H * W * WRW_CI;
+        const float* dyi = dy + n * H * W * Cout + slice * WRW_OT;
+        WrwStage st;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {                    // x: float4 idx of the segment -> pixel idx / 16 (column c0 - 1 + it), quad idx % 16
+            const int idx = tid + 256 * u, col = c0 - 1 + (idx >> 4);
+            st.xok[u] = idx < WRW_XF4 && col >= 0 && col < W;
+            st.xoff[u] = (long long)(col < 0 ? 0 : (col < W ? col : W - 1)) * WRW_CI + 4 * (idx & 15);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                    // dy: pixel idx / 16 (column c0 + it)
+            const int idx = tid + 256 * u, col = c0 + (idx >> 4);
+            st.dok[u] = col < W;
+            st.doff[u] = (long long)(col < W ? col : W - 1) * Cout + 4 * (idx & 15);
+        }
+        // the first step's operands: x rows r0 - 1, r0, r0 + 1 into slots 0, 1, 2 and dy row r0 (the barrier that ended the
+        // previous job's last step has every wave past its reads)
+        f32x4 vx[3], vd[2];
+        wrw_load_dy(dyi, st, r0, H, W, Cout, vd);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, vx);
+            wrw_loads_landed(vx, vd);
+            wrw_store_x(xs, t, st, rok, vx);
+        }
+        wrw_store_dy(ds, 0, st, vd);
+        __syncthreads();
+        for (int k = 0; k < nrows; ++k) {                // output row r0 + k: x rows r0 + k - 1 .. + 1 are ring entries k, k + 1, k + 2
+            // the next step's new segments: in flight while this step's MFMAs run.  (A job's last step loads and stores them for
+            // nothing: ring entry and dy buffer are the ones the next job's first step does not use)
+            const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, vx);
+            wrw_load_dy(dyi, st, r0 + k + 1, H, W, Cout, vd);
+            const float* A = ds + (k & 1) * WRW_DYROW + aoff;
+            const float* B0 = xs + (k & 3) * WRW_XROW + boff;
+            const float* B1 = xs + ((k + 1) & 3) * WRW_XROW + boff;
+            const float* B2 = xs + ((k + 2) & 3) * WRW_XROW + boff;
+            float a = *HK_LDS_CONST(A), b[9];
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                b[kw] = *HK_LDS_CONST(B0 + kw * WRW_CI);
+                b[3 + kw] = *HK_LDS_CONST(B1 + kw * WRW_CI);
+                b[6 + kw] = *HK_LDS_CONST(B2 + kw * WRW_CI);
+            }
+#pragma unroll
+            for (int p = 0; p < WRW_SW / 2; ++p) {       // pixel pair (2 p, 2 p + 1): the reads of pair p + 1 go out before the MFMAs of pair p
+                float an = 0.f, bn[9];
+                if (p + 1 < WRW_SW / 2) {
+                    an = *HK_LDS_CONST(A + (2 * p + 2) * WRW_OT);
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        bn[kw] = *HK_LDS_CONST(B0 + (2 * p + 2 + kw) * WRW_CI);
+                        bn[3 + kw] = *HK_LDS_CONST(B1 + (2 * p + 2 + kw) * WRW_CI);
+                        bn[6 + kw] = *HK_LDS_CONST(B2 + (2 * p + 2 + kw) * WRW_CI);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < 9; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[t], acc[t], 0, 0, 0);
+                if (p + 1 < WRW_SW / 2) {
+                    a = an;
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) b[t] = bn[t];
+                }
+            }
+            // ring entry k + 3 replaces entry k - 1, dy buffer (k + 1) & 1 row k - 1: last read a barrier ago
+            wrw_loads_landed(vx, vd);
+            wrw_store_x(xs, (k + 3) & 3, st, rok, vx);
+            wrw_store_dy(ds, (k + 1) & 1, st, vd);
+            __syncthreads();
+        }
+    }
+    // C layout of the 32 x 32 MFMA: column = lane & 31 (input channel), row = 8 (i / 4) + 4 (lane >> 5) + i % 4 (output channel)
+    float* pb = part + ((long long)blockIdx.x * Cout + slice * WRW_OT + oh * 32 + 4 * hf) * (9 * WRW_CI) + ch * 32 + l31;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pb[(8 * (i >> 2) + (i & 3)) * (9 * WRW_CI) + t * WRW_CI] = acc[t][i];
+}
+
+// The split of a problem into jobs and workgroups: the row-block height whose heaviest workgroup has the fewest row steps
+// (a block costs its rows + the two rows that prime the ring), the lowest block count among equals
+struct WrwPlan {
+    int nstrips, nrb, rpb, njobs, nwg;
+};
+static bool wrw_plan(int N, int H, int W, int slices, WrwPlan& pl) {
+    // two workgroups per CU over all slices (two waves per SIMD cover each other's LDS waits: conv1_2 6.54 ms against 6.72 with one)
+    int wgmax = tuning().wrw_wgs > 0 ? tuning().wrw_wgs : (slices <= 8 ? 512 / slices : 64);
+    if (wgmax > WRW_MAX_WG) wgmax = WRW_MAX_WG;
+    const long long nstrips = ((long long)W + WRW_SW - 1) / WRW_SW, base = (long long)N * nstrips;
+    long long best = -1;
+    for (int cand = 1; cand <= (H / WRW_MIN_ROWS > 1 ? H / WRW_MIN_ROWS : 1); ++cand) {
+        const int rpb = (H + cand - 1) / cand, nrb = (H + rpb - 1) / rpb;
+        if (nrb != cand) continue;
+        const long long jobs = base * nrb;
+        if (jobs > 0x7fffffffll) break;
+        const long long wg = jobs < wgmax ? jobs : wgmax;
+        const long long cost = ((jobs + wg - 1) / wg) * (rpb + 2);
+        if (best < 0 || cost < best) {
+            best = cost;
+            pl.nstrips = (int)nstrips; pl.nrb = nrb; pl.rpb = rpb; pl.njobs = (int)jobs; pl.nwg = (int)wg;
+        }
+    }
+    return best >= 0;
+}
+
+}  // namespace hk
+
+using namespace hk;
+
+extern "C" size_t hk_conv3x3_wrw_ws_bytes(int Cin, int Cout) {      // (for any sizes > 0: the workspace check comes before the shape check)
+    return Cin > 0 && Cout > 0 ? (size_t)WRW_MAX_WG * Cout * 9 * Cin * sizeof(float) : 0;
+}
+
+extern "C" int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N, int H, int W, int Cin, int Cout, void* ws,
+                              size_t ws_bytes, hk_stream_t stream) {
+    if (!dy || !x || !dw || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return HK_ERR_BAD_ARG;
+    if (!ws || ws_bytes < hk_conv3x3_wrw_ws_bytes(Cin, Cout)) return HK_ERR_WORKSPACE;
+    if (Cin != WRW_CI || Cout % WRW_OT != 0 || Cout / WRW_OT > 65535 || !aligned16(dy) || !aligned16(x) || !aligned16(dw) || !aligned16(ws))
+        return HK_ERR_UNSUPPORTED;
+    WrwPlan pl;
+    if (!wrw_plan(N, H, W, Cout / WRW_OT, pl)) return HK_ERR_UNSUPPORTED;
+    float* part = (float*)ws;
+    hipLaunchKernelGGL(conv3x3_wrw_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), 0, (hipStream_t)stream, dy, x, part,
+                       H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
+    HK_LAUNCH_CHECK();
+    const int nel = Cout * 9 * WRW_CI;
+    hipLaunchKernelGGL(partial_sum_kernel<16>, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, pl.nwg, nel, nel,
+                       dw, (float*)nullptr);
+    HK_LAUNCH_CHECK();
+    return HK_OK;
+}

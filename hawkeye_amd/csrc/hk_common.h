@@ -55,6 +55,9 @@ struct Tuning {
                             //                  (one launch), -1: always GEMM + dot product + bcnn_rank1_fix_kernel
     int sched_b = 0;        // HK_SCHED_B       > 0: work-split heuristics that depend on the batch size behave as if it were this (tests: the
                             //                  large-batch schedules on small inputs); results do not depend on it
+    int conv_wrw = 1;       // HK_CONV_WRW      weight gradient of the trunk's 64-input-channel 3 x 3 convolutions: 1: hk_conv3x3_wrw where it is the
+                            //                  measured winner (functional.conv3x3_wrw_ok), 0: the library's everywhere
+    int wrw_wgs = 0;        // HK_WRW_WGS       hk_conv3x3_wrw: workgroups per 64-wide Cout slice, at most (0: two per CU over all slices; up to 512)
 };
 Tuning& tuning();           // api.hip
 

@@ -19,6 +19,7 @@
 // applies ReLU's mask (y > 0  <=>  p > 0 at the argmax).  db is summed in a fixed order (per thread over its rows, threads of
 // a column quad in order, workgroups in order): deterministic, no atomics.
 #include "hk_common.h"
+#include "hk_partial_sum.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -515,34 +516,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
     }
 }
 
-// dwt [NT][64] and db [64] = the workgroup partials added in a fixed order: 64 elements per workgroup, sixteen interleaved chains
-// per element (eight loads in flight each), combined in order
-__global__ __launch_bounds__(1024) void conv1_bwd_final_kernel(const float* __restrict__ part, int nblk, int nel, int nt64,
-                                                               float* __restrict__ dwt, float* __restrict__ db) {
-    __shared__ float red[16][64];
-    const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + l;
-    float s = 0.f;
-    if (e < nel) {
-        int k = q;
-        for (; k + 7 * 16 < nblk; k += 8 * 16) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = part[(long long)(k + 16 * u) * nel + e];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; k < nblk; k += 16) s += part[(long long)k * nel + e];
-    }
-    red[q][l] = s;
-    __syncthreads();
-    if (q == 0 && e < nel) {
-        float t = red[0][l];
-        for (int k = 1; k < 16; ++k) t += red[k][l];
-        if (e < nt64) dwt[e] = t;
-        else db[e - nt64] = t;
-    }
-}
+// dwt [NT][64] and db [64] = the workgroup partials added in a fixed order: partial_sum_kernel (hk_partial_sum.h)
 
 constexpr int C1_BWD_BLOCKS = 1024;          // four workgroups per CU: sixteen waves to hide a step's load latency behind the others' FMAs
 
@@ -587,7 +561,7 @@ extern "C" int hk_conv1_bias_relu_bwd(const float* dy, const uint8_t* mask, cons
     }
     HK_LAUNCH_CHECK();
     const int nel = (9 * Cin + 1) * 64;
-    hipLaunchKernelGGL(conv1_bwd_final_kernel, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, (int)nblk, nel,
+    hipLaunchKernelGGL(partial_sum_kernel<16>, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, (int)nblk, nel,
                        9 * Cin * 64, dwt, dbias);
     HK_LAUNCH_CHECK();
     return HK_OK;

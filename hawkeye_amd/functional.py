@@ -1184,6 +1184,84 @@ def conv1_bias_relu(x, weight, bias):
     return _Conv1BiasReLU.apply(x, weight, bias)
 
 
+def _two(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def conv3x3_wrw_route(cout, n, h, w):
+    """The dispatch rule of hk_conv3x3_wrw, by measurement (in-step kernel times at batch 64 and 16 against the
+    library's weight gradient of the same layer): every supported layer goes to the kernel unless the `conv_wrw` knob is 0."""
+    import ctypes
+    v = ctypes.c_int(1)
+    check(_lib.load().hk_tuning_get(b'conv_wrw', ctypes.byref(v)), 'hk_tuning_get(conv_wrw)')
+    return v.value != 0
+
+
+def conv3x3_wrw_ok(x, conv):
+    """Whether hk_conv3x3_wrw computes this convolution's weight gradient: Conv2d(64, 64 k, 3, stride 1, padding 1) with a
+    channels_last fp32 weight, on an fp32 channels_last HIP map, and the dispatch rule (conv3x3_wrw_route) sends the layer there.
+    Anything else keeps the library's weight gradient (model/backbone/vgg.py)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return False
+    w = conv.weight
+    if not (w.dtype == torch.float32 and w.device == x.device and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if not (conv.in_channels == 64 and x.shape[1] == 64 and conv.out_channels > 0 and conv.out_channels % 64 == 0
+            and _two(conv.kernel_size) == (3, 3) and _two(conv.stride) == (1, 1) and _two(conv.padding) == (1, 1)
+            and _two(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'):
+        return False
+    return conv3x3_wrw_route(conv.out_channels, x.shape[0], x.shape[2], x.shape[3])
+
+
+def conv3x3_wrw_raw(x, dy):
+    """dW [Cout, 64, 3, 3] (channels_last strides over the kernel's [Cout][3][3][64] buffer, no copy) of conv2d(x, W, padding=1) from
+    the channels_last maps x [N, 64, H, W] and dy [N, Cout, H, W]; raises where hk_conv3x3_wrw does not serve the call."""
+    lib = _lib.load()
+    _nhwc(x, 'conv3x3_wrw')
+    _nhwc(dy, 'conv3x3_wrw')
+    n, cin, h, w = x.shape
+    cout = dy.shape[1]
+    if tuple(dy.shape) != (n, cout, h, w) or x.numel() == 0 or dy.numel() == 0:
+        raise _lib.HawkeyeHipError(f'conv3x3_wrw: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}')
+    px, pdy = ptr(x), ptr(dy)                      # (a CPU tensor is refused here, before anything is allocated)
+    buf = torch.empty(cout, 3, 3, cin, dtype=torch.float32, device=x.device)
+    nws = lib.hk_conv3x3_wrw_ws_bytes(cin, cout)
+    ws = _ws(nws, x.device)
+    check(lib.hk_conv3x3_wrw(pdy, px, ptr(buf), n, h, w, cin, cout, ptr(ws), nws, stream()), 'hk_conv3x3_wrw')
+    return buf.permute(0, 3, 1, 2)
+
+
+class _Conv3x3Wrw(torch.autograd.Function):
+    """conv2d(x, weight, None, stride 1, padding 1) for 64 input channels: the forward and the input gradient are the library's, the
+    weight gradient is hk_conv3x3_wrw's (csrc/conv_wrw.hip) - the library's own for these layers (model/backbone/vgg.py:24-57,
+    `features[2]` and `features[5]`) runs a 64 x 64 tile with split-K atomics behind a zero-fill."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        return torch.nn.functional.conv2d(x, weight, None, 1, 1, 1, 1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        if dy.dtype != torch.float32:
+            raise _lib.HawkeyeHipError(f'conv3x3_wrw backward: fp32 only, got {dy.dtype}')
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.ops.aten.convolution_backward(dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                                                     (True, False, False))[0]
+        if ctx.needs_input_grad[1]:
+            dw = conv3x3_wrw_raw(x, dy)
+        return dx, dw
+
+
+def conv3x3_wrw(x, weight):
+    """conv2d(x, weight, None, stride=1, padding=1) with the weight gradient on hk_conv3x3_wrw; see _Conv3x3Wrw."""
+    return _Conv3x3Wrw.apply(x, weight)
+
+
 def bias_relu(x, bias):
     """relu(x + bias[None,:,None,None]) in place on x (a channels_last convolution output); see _BiasReLU."""
     return _BiasReLU.apply(x, bias)

@@ -24,7 +24,8 @@ class ConvStack(nn.Sequential):
     convolution the bias add, the ReLU and, at the end of a stage, the 2 x 2 max-pool are one pass over the activation
     instead of one pass per op (hk_bias_relu_*, csrc/trunk.hip: the framework's elementwise kernels around the
     convolutions are 12.5 % of the BCNN training step, and the full-resolution activation in front of a pool is not
-    even written).  The convolutions themselves are MIOpen's.  Anything the kernels do not cover - CPU tensors, NCHW
+    even written).  The convolutions themselves are MIOpen's, but for the first layer (hk_conv1_bias_relu_*) and the weight
+    gradient of the two layers with 64 input channels (hk_conv3x3_wrw, csrc/conv_wrw.hip).  Anything the kernels do not cover - CPU tensors, NCHW
     memory, odd map sizes, other dtypes, a child with forward hooks - runs the children one by one as nn.Sequential does."""
 
     def forward(self, x):
@@ -44,7 +45,11 @@ class ConvStack(nn.Sequential):
                     x = HF.conv1_bias_relu(x, m.weight, m.bias)
                     i += 2
                     continue
-                y = TF.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
+                if HF.conv3x3_wrw_ok(x, m):
+                    # 64 input channels: the library's forward and input gradient, the weight gradient on hk_conv3x3_wrw
+                    y = HF.conv3x3_wrw(x, m.weight)
+                else:
+                    y = TF.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
                 pool = i + 2 < len(mods) and _plain_pool(mods[i + 2])
                 if pool and HF.trunk_epilogue_ok(y, pool=True):
                     x = HF.bias_relu_pool(y, m.bias)

@@ -63,6 +63,9 @@ const char* hk_version(void);
  *   "lin_walk"      classifier backward: 1 workgroup s walks the 64-feature chunks s, s + S, ..; 0 a contiguous slab per
  *                   workgroup; -1 (default) the measured winner per kernel
  *   "sched_b"       > 0: batch-size dependent work splits behave as if the batch were this (tests)
+ *   "conv_wrw"      1 (default): the trunk routes the weight gradient of its 64-input-channel 3 x 3 convolutions to
+ *                   hk_conv3x3_wrw where that is the measured winner; 0: the library's weight gradient everywhere
+ *   "wrw_wgs"       hk_conv3x3_wrw: workgroups per 64-wide Cout slice, at most (0 = two per CU over all slices; up to 512)
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
@@ -292,6 +295,17 @@ int hk_conv1_bias_relu_fwd(const float* x, const float* wt, const float* bias, f
                            int Cout, hk_stream_t stream);
 int hk_conv1_bias_relu_bwd(const float* dy, const uint8_t* mask, const float* x, float* dwt, float* dbias, int N, int H, int W, int Cin,
                            int Cout, void* ws, size_t ws_bytes, hk_stream_t stream);
+/* Weight gradient of a 3 x 3 convolution with 64 input channels (stride 1, padding 1, dilation 1, fp32; the trunk's conv1_2 and conv2_1,
+ * model/backbone/vgg.py:24-57), on the matrix pipe with the whole 64 x 576 result of a Cout slice in one workgroup's accumulators:
+ *   x [N][H][W][64], dy [N][H][W][Cout] (channels_last maps) -> dw [Cout][3][3][64] (a channels_last [Cout, 64, 3, 3] weight),
+ *   dw[o][kh][kw][c] = sum over n, h, w of dy[n][h][w][o] x[n][h + kh - 1][w + kw - 1][c], zero outside the image.
+ * Cin == 64, Cout % 64 == 0, 16-byte aligned pointers, any N, H, W >= 1; HK_ERR_UNSUPPORTED (nothing launched) otherwise.  Workspace
+ * hk_conv3x3_wrw_ws_bytes(Cin, Cout) bytes (per-workgroup partial results, added in a fixed order: no atomics, no zero-fill, the same
+ * input gives the same bits).  Nothing outside the two maps is read.  Replaces the library's weight gradient for those layers; the
+ * forward and the input gradient stay the library's. */
+size_t hk_conv3x3_wrw_ws_bytes(int Cin, int Cout);
+int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
+                   hk_stream_t stream);
 int hk_add_relu_fwd(float* a, const float* b, long long n, hk_stream_t stream);
 int hk_relu_mask_bwd(const float* dy, const float* y, float* g, long long n, hk_stream_t stream);
 
