@@ -93,6 +93,8 @@ SIGNATURES = {
     'hk_linear_bwd_scaled': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     'hk_npairs_ws_bytes': (c_sz, [c_i, c_i]),
     'hk_npairs_loss': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_peer_loss_ws_bytes': (c_sz, [c_i, c_i]),
+    'hk_peer_loss': (c_i, [c_f, c_f, c_f, ctypes.c_double, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_sz, c_f]),
     'hk_cin_sci_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_sci_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_cci_fwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),

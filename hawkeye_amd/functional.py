@@ -811,6 +811,75 @@ def npairs_loss(parts, targets):
     return _NPairsLoss.apply(parts, targets)
 
 
+# --------------------------------------------------------------------- peer-learning loss
+def _peer_args(logits_1, logits_2, labels, drop_rate):
+    if logits_1.dim() != 2 or logits_1.shape != logits_2.shape:
+        raise _lib.HawkeyeHipError(f'peer_learning_loss: logits of shapes {tuple(logits_1.shape)} and {tuple(logits_2.shape)}; '
+                                   f'two [N, C] matrices of one shape are needed')
+    if logits_1.device != logits_2.device:
+        raise _lib.HawkeyeHipError(f'peer_learning_loss: logits on {logits_1.device} and {logits_2.device}')
+    l1, l2 = _f32c(logits_1), _f32c(logits_2)          # dense copies of views; the kernels read rows of C floats
+    n = l1.shape[0]
+    if labels.is_floating_point() or labels.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'peer_learning_loss: labels must be integers; got {labels.dtype}')
+    if tuple(labels.shape) != (n,):
+        raise _lib.HawkeyeHipError(f'peer_learning_loss: {n} rows but labels of shape {tuple(labels.shape)}')
+    y = labels.to(device=l1.device, dtype=torch.int32).contiguous()       # converted on the device, no host round trip
+    return l1, l2, y, float(drop_rate)
+
+
+def _peer_call(l1, l2, y, drop_rate):
+    lib = _lib.load()
+    n, c = l1.shape
+    loss = torch.empty(2, dtype=torch.float32, device=l1.device)
+    dl1, dl2 = torch.empty_like(l1), torch.empty_like(l2)
+    stats = torch.empty(4, dtype=torch.int32, device=l1.device)
+    nws = lib.hk_peer_loss_ws_bytes(n, c)
+    ws = _ws(nws, l1.device)
+    check(lib.hk_peer_loss(ptr(l1), ptr(l2), ptr(y), drop_rate, ptr(loss), ptr(dl1), ptr(dl2), ptr(stats), n, c, ptr(ws),
+                           nws, stream()), 'hk_peer_loss')
+    return loss, dl1, dl2, stats
+
+
+class _PeerLearningLoss(torch.autograd.Function):
+    """replaces PeerLearningLoss, model/loss/peer_learning_loss.py:5-65.  The kernel returns both losses and both
+    gradients in one pass; backward only scales them.  loss_1 depends on logits_1 alone and loss_2 on logits_2 alone
+    (the selection is not differentiated: the reference sorts `.data`)."""
+
+    @staticmethod
+    def forward(ctx, logits_1, logits_2, labels, drop_rate):
+        l1, l2, y, drop_rate = _peer_args(logits_1, logits_2, labels, drop_rate)
+        loss, dl1, dl2, stats = _peer_call(l1, l2, y, drop_rate)
+        ctx.save_for_backward(dl1, dl2)
+        ctx.mark_non_differentiable(stats)
+        return loss[0], loss[1], stats
+
+    @staticmethod
+    def backward(ctx, g1, g2, _g_stats):
+        dl1, dl2 = ctx.saved_tensors
+        return dl1 * g1, dl2 * g2, None, None
+
+
+def peer_learning_loss(logits_1, logits_2, labels, drop_rate):
+    """logits_1, logits_2 [N,C], labels [N], drop_rate (host float in [0, 1]) -> (loss_1, loss_2), each net's mean cross
+    entropy over the rows it keeps: every row on which the two argmaxes disagree, and of the n agreeing rows the
+    int((1 - drop_rate) n) its PEER ranks lowest in cross entropy."""
+    loss_1, loss_2, _ = _PeerLearningLoss.apply(logits_1, logits_2, labels, drop_rate)
+    return loss_1, loss_2
+
+
+def peer_learning_loss_with_stats(logits_1, logits_2, labels, drop_rate):
+    """peer_learning_loss plus the int32 device tensor [n, m, count_1, count_2] (agreeing rows, agreeing rows kept, rows in
+    each net's mean) - for tests and logging; nothing is read back to the host here."""
+    return _PeerLearningLoss.apply(logits_1, logits_2, labels, drop_rate)
+
+
+def peer_learning_stats(logits_1, logits_2, labels, drop_rate):
+    """Only the [n, m, count_1, count_2] device tensor of peer_learning_loss (no autograd)."""
+    with torch.no_grad():
+        return _peer_call(*_peer_args(logits_1, logits_2, labels, drop_rate))[3]
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

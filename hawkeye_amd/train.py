@@ -1,7 +1,7 @@
 """Trainer runtime with the reference's override points (train.py:37-435):
 get_model / get_transformers / get_dataset / get_dataloader / get_criterion /
 get_optimizer / get_scheduler / batch_training / batch_validate /
-do_scheduler_step / on_start_epoch / on_end_epoch, `@emergency_save`, checkpoint
+do_scheduler_step / update_performance_meter / on_start_epoch / on_end_epoch, `@emergency_save`, checkpoint
 layout `{epoch, model, optimizer, scheduler}`, `best_model.pth`.
 
 What changed underneath is only the device / parallel layer: instead of
@@ -272,8 +272,7 @@ class Trainer:
             dt = self.timer.tick()
             self.logger.info(f'Training epoch {epoch + 1} took {dt:.1f}s')
             self.sync_average_meters()
-            self.performance_meters['train']['acc'].update(self.average_meters['acc'].avg)
-            self.performance_meters['train']['loss'].update(self.average_meters['loss'].avg)
+            self.update_performance_meter('train')
             self.report(epoch=epoch + 1, split='train')
 
             self.reset_average_meters()
@@ -282,7 +281,7 @@ class Trainer:
             val_acc = self.average_meters['acc'].avg             # over the WHOLE validation set (validate() syncs ranks)
             m = self.performance_meters['val']['acc']
             is_best = epoch >= 5 and (not m.values or val_acc > m.best_value)     # train.py:284-288
-            m.update(val_acc)
+            self.update_performance_meter('val')
             self.report(epoch=epoch + 1, split='val')
             self.do_scheduler_step()
 
@@ -316,6 +315,15 @@ class Trainer:
         self.backward_and_step(loss)
         self.average_meters['acc'].update(accuracy(outputs, labels, 1), images.size(0))
         self.average_meters['loss'].update(loss.item(), images.size(0))
+
+    def update_performance_meter(self, split):
+        """End of an epoch's training / validation pass: the epoch averages go into the performance meters (the
+        reference's override point of the same name; a trainer with other meters than acc / loss overrides it)."""
+        if split == 'train':
+            self.performance_meters['train']['acc'].update(self.average_meters['acc'].avg)
+            self.performance_meters['train']['loss'].update(self.average_meters['loss'].avg)
+        else:
+            self.performance_meters['val']['acc'].update(self.average_meters['acc'].avg)
 
     def validate(self):
         self.model.train(False)

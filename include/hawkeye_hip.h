@@ -435,6 +435,25 @@ size_t hk_npairs_ws_bytes(int n, int D);
 int hk_npairs_loss(const float* x, const int32_t* labels, float* loss, float* dx, int b, int p, int D, void* ws,
                    size_t ws_bytes, hk_stream_t stream);
 
+/* -------------------------------------------------- Peer-learning loss (WebFG baseline) ----
+ * (loss_1, loss_2) = PeerLearningLoss(logits_1, logits_2, labels, drop_rate) and both logit gradients in one call.
+ * replaces model/loss/peer_learning_loss.py:5-65 (about forty small launches and two host synchronisations).
+ *   logits1, logits2 [N,C] ; labels int32 [N] ; drop_rate in [0, 1] (a host double)
+ *   rows on which the two nets' argmax agree (n of them) are ranked by their cross entropy per net; net 1 keeps the
+ *   m = (long long)((1 - drop_rate) n) rows net 2 finds easiest and the other way round; rows that disagree are always kept.
+ *   loss [2]: mean cross entropy of each net over its kept rows (NaN when it keeps none) ;
+ *   dl1, dl2 [N,C]: d loss_1 / d logits1, d loss_2 / d logits2 (zero rows where dropped; the selection is not differentiated) ;
+ *   stats int32 [4]: n, m, count_1, count_2 - written on the device, nothing is read back ;
+ *   a label outside [0, C) reads nothing and makes its row's cross entropy NaN.
+ *   ws: hk_peer_loss_ws_bytes(N, C).  No host synchronisation, no allocation: capturable in a hipGraph.
+ * One launch (both matrices resident in one workgroup's LDS) where 8 N C + 40 N + 128 bytes fit 160 KB, three launches
+ * otherwise - bit-identical results (knob peer_form).  HK_ERR_BAD_ARG: null pointer, N or C <= 0, drop_rate outside [0, 1]
+ * or NaN; HK_ERR_WORKSPACE: short workspace; HK_ERR_UNSUPPORTED: N > 2048 (what the selection kernel's LDS holds), or
+ * peer_form 2 at a shape the resident form cannot hold. */
+size_t hk_peer_loss_ws_bytes(int N, int C);
+int hk_peer_loss(const float* logits1, const float* logits2, const int32_t* labels, double drop_rate, float* loss, float* dl1,
+                 float* dl2, int32_t* stats, int N, int C, void* ws, size_t ws_bytes, hk_stream_t stream);
+
 /* ------------------------------------------------ CIN channel interaction (8f-2) ----
  * SCI: W = softmax_rows(-X X^T / HW), Y = W X ; CCI: Yc[b] = |W[b] - w_b W[(b + B/2) % B]| X[b].
  * replaces the bmm / softmax / abs / bmm parts of ChannelInteractionModule.forward,
