@@ -95,6 +95,13 @@ SIGNATURES = {
     'hk_npairs_loss': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_sz, c_f]),
     'hk_peer_loss_ws_bytes': (c_sz, [c_i, c_i]),
     'hk_peer_loss': (c_i, [c_f, c_f, c_f, ctypes.c_double, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_api_pairs': (c_i, [c_f, c_f, c_f, c_i, c_i, c_f]),
+    'hk_api_gather_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_f]),
+    'hk_api_gather_bwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_f]),
+    'hk_api_interact_fwd': (c_i, [c_f, c_f, c_f, c_f, c_fl, c_f, c_i, c_i, c_f]),
+    'hk_api_interact_bwd': (c_i, [c_f, c_f, c_f, c_f, c_fl, c_f, c_f, c_f, c_i, c_i, c_f]),
+    'hk_apinet_loss_ws_bytes': (c_sz, [c_i, c_i]),
+    'hk_apinet_loss': (c_i, [c_f, c_f, c_f, c_fl, c_fl, c_f, c_f, c_f, c_i, c_i, c_f, c_sz, c_f]),
     'hk_cin_sci_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_sci_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_cci_fwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),

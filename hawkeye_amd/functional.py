@@ -880,6 +880,182 @@ def peer_learning_stats(logits_1, logits_2, labels, drop_rate):
         return _peer_call(*_peer_args(logits_1, logits_2, labels, drop_rate))[3]
 
 
+# --------------------------------------------------------------------- APINet pairwise interaction
+def _api_pool(pool, what):
+    if pool.dim() != 2 or pool.shape[0] < 1 or pool.shape[1] < 1:
+        raise _lib.HawkeyeHipError(f'{what}: pool must be [B, D] pooled vectors, got {tuple(pool.shape)}')
+    return _f32c(pool)
+
+
+def _api_partner(partner, pool, what):
+    b = pool.shape[0]
+    if partner.is_floating_point() or partner.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'{what}: partner must be integers; got {partner.dtype}')
+    if tuple(partner.shape) != (2 * b,):
+        raise _lib.HawkeyeHipError(f'{what}: {b} rows need a partner of shape ({2 * b},), got {tuple(partner.shape)}')
+    if partner.device != pool.device:
+        raise _lib.HawkeyeHipError(f'{what}: pool on {pool.device} but partner on {partner.device}')
+    return partner.to(torch.int32).contiguous()
+
+
+def api_pairs(pool, labels):
+    """pool [B,D], labels [B] -> partner int32 [2B] on the device (no autograd, no host round trip): partner[i] the
+    nearest row of the same label (j != i), partner[B+i] the nearest row of another label; squared Euclidean distance,
+    ties to the lowest index, 0 where a row has no candidate.  replaces get_pairs, model/methods/APINet.py:76-91."""
+    pool = _api_pool(pool.detach(), 'api_pairs')
+    b, d = pool.shape
+    if labels.is_floating_point() or labels.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'api_pairs: labels must be integers; got {labels.dtype}')
+    if tuple(labels.shape) != (b,):
+        raise _lib.HawkeyeHipError(f'api_pairs: {b} rows but labels of shape {tuple(labels.shape)}')
+    y = labels.to(device=pool.device, dtype=torch.int32).contiguous()
+    lib = _lib.load()
+    partner = torch.empty(2 * b, dtype=torch.int32, device=pool.device)
+    check(lib.hk_api_pairs(ptr(pool), ptr(y), ptr(partner), b, d, stream()), 'hk_api_pairs')
+    return partner
+
+
+class _ApiPairFeatures(torch.autograd.Function):
+    """mutual = [pool[r mod B] | pool[partner[r]]].  replaces APINet.py:36-37,41 (four index gathers and three cats);
+    the backward is the deterministic scatter of hk_api_gather_bwd."""
+
+    @staticmethod
+    def forward(ctx, pool, partner):
+        lib = _lib.load()
+        pool = _api_pool(pool, 'api_pair_features')
+        partner = _api_partner(partner, pool, 'api_pair_features')
+        b, d = pool.shape
+        mutual = torch.empty(2 * b, 2 * d, dtype=torch.float32, device=pool.device)
+        check(lib.hk_api_gather_fwd(ptr(pool), ptr(partner), ptr(mutual), b, d, stream()), 'hk_api_gather_fwd')
+        ctx.save_for_backward(partner)
+        ctx.shape = (b, d)
+        return mutual
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (partner,) = ctx.saved_tensors
+        b, d = ctx.shape
+        g = _f32c(g)
+        dpool = torch.empty(b, d, dtype=torch.float32, device=g.device)
+        check(lib.hk_api_gather_bwd(ptr(g), ptr(partner), ptr(dpool), b, d, stream()), 'hk_api_gather_bwd')
+        return dpool, None
+
+
+def api_pair_features(pool, partner):
+    """pool [B,D], partner [2B] (api_pairs) -> mutual [2B,2D]: each row next to its partner, intra pairs first."""
+    return _ApiPairFeatures.apply(pool, partner)
+
+
+class _ApiInteract(torch.autograd.Function):
+    """The gates and the four gated feature blocks in one launch each way.  replaces APINet.py:46-61 (and, through the
+    row order of `feats`, the zeros + slice copies of :63-68)."""
+
+    @staticmethod
+    def forward(ctx, pool, partner, m, masks, drop_p):
+        lib = _lib.load()
+        pool = _api_pool(pool, 'api_interact')
+        partner = _api_partner(partner, pool, 'api_interact')
+        b, d = pool.shape
+        if tuple(m.shape) != (2 * b, d):
+            raise _lib.HawkeyeHipError(f'api_interact: m must be [2B, D] = [{2 * b}, {d}], got {tuple(m.shape)}')
+        if m.device != pool.device:
+            raise _lib.HawkeyeHipError(f'api_interact: pool on {pool.device} but m on {m.device}')
+        m = _f32c(m)
+        scale = 1.0
+        if masks is not None:
+            if masks.dtype not in (torch.bool, torch.uint8):
+                raise _lib.HawkeyeHipError(f'api_interact: keep-masks must be bool or uint8; got {masks.dtype}')
+            if tuple(masks.shape) != (8 * b, d):
+                raise _lib.HawkeyeHipError(f'api_interact: keep-masks must be [8B, D] = [{8 * b}, {d}], got {tuple(masks.shape)}')
+            if masks.device != pool.device:
+                raise _lib.HawkeyeHipError(f'api_interact: pool on {pool.device} but masks on {masks.device}')
+            if not 0.0 <= drop_p < 1.0:
+                raise _lib.HawkeyeHipError(f'api_interact: drop_p must lie in [0, 1); got {drop_p}')
+            masks = masks.contiguous().view(torch.uint8)
+            scale = 1.0 / (1.0 - drop_p)
+        feats = torch.empty(8 * b, d, dtype=torch.float32, device=pool.device)
+        check(lib.hk_api_interact_fwd(ptr(pool), ptr(partner), ptr(m), ptr(masks), scale, ptr(feats), b, d, stream()),
+              'hk_api_interact_fwd')
+        ctx.save_for_backward(pool, partner, m, masks)
+        ctx.scale = scale
+        return feats
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        pool, partner, m, masks = ctx.saved_tensors
+        b, d = pool.shape
+        g = _f32c(g)
+        dm, dpool = torch.empty_like(m), torch.empty_like(pool)
+        check(lib.hk_api_interact_bwd(ptr(pool), ptr(partner), ptr(m), ptr(masks), ctx.scale, ptr(g), ptr(dm), ptr(dpool), b, d,
+                                      stream()), 'hk_api_interact_bwd')
+        return dpool, None, dm, None, None
+
+
+def api_interact(pool, partner, m, masks=None, drop_p=0.5):
+    """pool [B,D], partner [2B], m [2B,D] (= map2(drop(map1(mutual)))) -> feats [8B,D] in the row order 1-self, 2-self,
+    1-other, 2-other, so that fc(feats) split in half is (self_logits, other_logits).  masks: bool / uint8 [8B,D]
+    keep-masks of the four dropouts (kept elements are scaled by 1 / (1 - drop_p)); None: no dropout."""
+    return _ApiInteract.apply(pool, partner, m, masks, float(drop_p))
+
+
+def _apinet_loss_args(self_logits, other_logits, labels1, labels2, what='apinet_loss'):
+    if self_logits.dim() != 2 or self_logits.shape != other_logits.shape:
+        raise _lib.HawkeyeHipError(f'{what}: logits of shapes {tuple(self_logits.shape)} and {tuple(other_logits.shape)}; '
+                                   f'two [R, C] matrices of one shape are needed')
+    if self_logits.device != other_logits.device:
+        raise _lib.HawkeyeHipError(f'{what}: logits on {self_logits.device} and {other_logits.device}')
+    ls, lo = _f32c(self_logits), _f32c(other_logits)
+    r = ls.shape[0]
+    for y in (labels1, labels2):
+        if y.is_floating_point() or y.dtype == torch.bool:
+            raise _lib.HawkeyeHipError(f'{what}: labels must be integers; got {y.dtype}')
+    if labels1.dim() != 1 or labels1.shape != labels2.shape or 2 * labels1.shape[0] != r:
+        raise _lib.HawkeyeHipError(f'{what}: {r} rows need labels1 and labels2 of shape ({r // 2},) each, got '
+                                   f'{tuple(labels1.shape)} and {tuple(labels2.shape)}')
+    y = torch.cat([labels1, labels2]).to(device=ls.device, dtype=torch.int32)        # on the device, no host round trip
+    return ls, lo, y
+
+
+class _APINetLoss(torch.autograd.Function):
+    """replaces APINetLoss.__call__, model/loss/APINet_loss.py:29-39.  The kernel returns the three loss terms and both
+    logit gradients of the total in one call; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, self_logits, other_logits, labels1, labels2, label_smoothing, margin):
+        ls, lo, y = _apinet_loss_args(self_logits, other_logits, labels1, labels2)
+        lib = _lib.load()
+        r, c = ls.shape
+        loss = torch.empty(3, dtype=torch.float32, device=ls.device)
+        ds, do = torch.empty_like(ls), torch.empty_like(lo)
+        nws = lib.hk_apinet_loss_ws_bytes(r, c)
+        ws = _ws(nws, ls.device)
+        check(lib.hk_apinet_loss(ptr(ls), ptr(lo), ptr(y), label_smoothing, margin, ptr(loss), ptr(ds), ptr(do), r, c, ptr(ws),
+                                 nws, stream()), 'hk_apinet_loss')
+        ctx.save_for_backward(ds, do)
+        parts = loss[1:]
+        ctx.mark_non_differentiable(parts)
+        return loss[0], parts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        ds, do = ctx.saved_tensors
+        return ds * g, do * g, None, None, None, None
+
+
+def apinet_loss(self_logits, other_logits, labels1, labels2, label_smoothing=0.1, margin=0.05):
+    """self_logits, other_logits [4B,C], labels1, labels2 [2B] (APINet's training outputs) -> the scalar loss: cross
+    entropy with label smoothing over cat(self, other) against the fourfold targets, plus the mean hinge
+    max(0, p_other[y] - p_self[y] + margin)."""
+    return _APINetLoss.apply(self_logits, other_logits, labels1, labels2, float(label_smoothing), float(margin))[0]
+
+
+def apinet_loss_with_parts(self_logits, other_logits, labels1, labels2, label_smoothing=0.1, margin=0.05):
+    """apinet_loss plus the device tensor [CE, rank] of its two terms (not differentiable) - for logging and tests."""
+    return _APINetLoss.apply(self_logits, other_logits, labels1, labels2, float(label_smoothing), float(margin))
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

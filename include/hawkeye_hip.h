@@ -454,6 +454,37 @@ size_t hk_peer_loss_ws_bytes(int N, int C);
 int hk_peer_loss(const float* logits1, const float* logits2, const int32_t* labels, double drop_rate, float* loss, float* dl1,
                  float* dl2, int32_t* stats, int N, int C, void* ws, size_t ws_bytes, hk_stream_t stream);
 
+/* ------------------------------------------------ APINet pairwise-interaction head ----
+ * replaces model/methods/APINet.py:34-68,76-113 and model/loss/APINet_loss.py:29-39.  Every entry point: fp32, no host
+ * synchronisation, no allocation (capturable in a hipGraph), no float atomics, fixed summation orders - the same bits on
+ * every run.  HK_ERR_BAD_ARG: null pointer (masks may be NULL), B / D / R / C <= 0, scale not a positive finite number,
+ * smoothing outside [0, 1], margin not finite; HK_ERR_UNSUPPORTED: 2 B > 65535 rows; HK_ERR_WORKSPACE: short workspace.
+ *   pool [B,D] pooled vectors ; labels int32 [B] ; partner int32 [2B]
+ *   hk_api_pairs: partner[i] = the nearest row j != i with labels[j] == labels[i], partner[B + i] = the nearest row with
+ *     another label; squared Euclidean distance as sum (a - b)^2 in a fixed order (not the reference's cancelling
+ *     -2ab + |a|^2 + |b|^2); ties go to the lowest index; a NaN distance counts as +inf; no candidate: 0.
+ *   hk_api_gather_fwd: mutual [2B,2D], row r = [pool[r mod B] | pool[partner[r]]] ; hk_api_gather_bwd: dmutual -> dpool
+ *     (row i gathers from the rows i, B + i and every r with partner[r] == i, r ascending).
+ *   hk_api_interact_fwd: m [2B,D] ; f1 = pool[r mod B], f2 = pool[partner[r]], g1 = sigmoid(m f1), g2 = sigmoid(m f2) ;
+ *     feats [8B,D] = [f1 (1 + g1) ; f2 (1 + g2) ; f1 (1 + g2) ; f2 (1 + g1)], each element times scale where
+ *     masks uint8 [8B,D] is non-zero and 0 where it is zero (masks NULL: no dropout, scale ignored).
+ *   hk_api_interact_bwd: dfeats [8B,D] -> dm [2B,D], dpool [B,D] (the same scatter order; one launch, gates recomputed).
+ *   A partner outside [0, B) is never dereferenced: its f2 reads as zeros and it scatters nothing.
+ *   hk_apinet_loss: self_logits, other_logits [R,C] (R = 4 x batch) ; labels int32 [R] = cat(labels1, labels2) ;
+ *     loss [3] = total, CE, rank with CE = label-smoothed cross entropy averaged over the 2R rows of cat(self, other) and
+ *     rank = mean_r max(0, p_other[r, y_r] - p_self[r, y_r] + margin) ; dself, dother [R,C] = d total / d logits.
+ *     A label outside [0, C) reads nothing and makes the loss NaN.  ws: hk_apinet_loss_ws_bytes(R, C). */
+int hk_api_pairs(const float* pool, const int32_t* labels, int32_t* partner, int B, int D, hk_stream_t stream);
+int hk_api_gather_fwd(const float* pool, const int32_t* partner, float* mutual, int B, int D, hk_stream_t stream);
+int hk_api_gather_bwd(const float* dmutual, const int32_t* partner, float* dpool, int B, int D, hk_stream_t stream);
+int hk_api_interact_fwd(const float* pool, const int32_t* partner, const float* m, const uint8_t* masks, float scale,
+                        float* feats, int B, int D, hk_stream_t stream);
+int hk_api_interact_bwd(const float* pool, const int32_t* partner, const float* m, const uint8_t* masks, float scale,
+                        const float* dfeats, float* dm, float* dpool, int B, int D, hk_stream_t stream);
+size_t hk_apinet_loss_ws_bytes(int R, int C);
+int hk_apinet_loss(const float* self_logits, const float* other_logits, const int32_t* labels, float smoothing, float margin,
+                   float* loss, float* dself, float* dother, int R, int C, void* ws, size_t ws_bytes, hk_stream_t stream);
+
 /* ------------------------------------------------ CIN channel interaction (8f-2) ----
  * SCI: W = softmax_rows(-X X^T / HW), Y = W X ; CCI: Yc[b] = |W[b] - w_b W[(b + B/2) % B]| X[b].
  * replaces the bmm / softmax / abs / bmm parts of ChannelInteractionModule.forward,
