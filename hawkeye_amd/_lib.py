@@ -102,6 +102,10 @@ SIGNATURES = {
     'hk_api_interact_bwd': (c_i, [c_f, c_f, c_f, c_f, c_fl, c_f, c_f, c_f, c_i, c_i, c_f]),
     'hk_apinet_loss_ws_bytes': (c_sz, [c_i, c_i]),
     'hk_apinet_loss': (c_i, [c_f, c_f, c_f, c_fl, c_fl, c_f, c_f, c_f, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_nts_nms': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_f]),
+    'hk_nts_crop_resize': (c_i, [c_f, c_f, c_f] + [c_i] * 8 + [c_f]),
+    'hk_nts_loss_ws_bytes': (c_sz, [c_i, c_i, c_i]),
+    'hk_nts_loss': (c_i, [c_f] * 5 + [c_fl] + [c_f] * 5 + [c_i, c_i, c_i, c_f, c_sz, c_f]),
     'hk_cin_sci_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_sci_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_cci_fwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),

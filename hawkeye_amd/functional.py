@@ -1056,6 +1056,122 @@ def apinet_loss_with_parts(self_logits, other_logits, labels1, labels2, label_sm
     return _APINetLoss.apply(self_logits, other_logits, labels1, labels2, float(label_smoothing), float(margin))
 
 
+# --------------------------------------------------------------------- NTS-Net proposals, part crops, loss
+def _nts_int(t, shape, device, what, name):
+    if t.is_floating_point() or t.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'{what}: {name} must be integers; got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.HawkeyeHipError(f'{what}: {name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    if t.device != device:
+        raise _lib.HawkeyeHipError(f'{what}: {name} on {t.device} but the data on {device}')
+    return t.to(torch.int32).contiguous()
+
+
+def nts_nms(scores, anchors, topn, iou_thresh=0.25):
+    """scores [B,A], anchors integer [A,4] = y0, x0, y1, x1 -> (index int64 [B,topn], boxes int32 [B,topn,4]) on the
+    device, no autograd, no host round trip.  replaces hard_nms (model/methods/NTS_Net/anchors.py:63-90) and the numpy
+    plumbing around it (NTSNet.py:35-41): greedy, highest live score first, a live anchor survives a pick only with
+    IoU < iou_thresh (strictly; corner differences without + 1, evaluated in float64 as the reference does).  Equal
+    scores go to the highest index - what a stable ascending sort read from its end gives; the reference's argsort is
+    not stable there.  A slot that no live anchor can fill repeats the last chosen anchor: the reference builds a ragged
+    array and fails on it; with the default anchor set (426 or 1614 anchors, topn 6) that cannot happen.  hard_nms also
+    stops when every remaining row is all zeros (`res.any()`); that quirk is not reproduced.  A <= 2048."""
+    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise _lib.HawkeyeHipError(f'nts_nms: scores must be [B, A], got {tuple(scores.shape)}')
+    scores = _f32c(scores.detach())
+    b, a = scores.shape
+    topn = int(topn)
+    if topn < 1:
+        raise _lib.HawkeyeHipError(f'nts_nms: topn must be positive; got {topn}')
+    anchors = _nts_int(anchors, (a, 4), scores.device, 'nts_nms', 'anchors')
+    lib = _lib.load()
+    index = torch.empty(b, topn, dtype=torch.int32, device=scores.device)
+    boxes = torch.empty(b, topn, 4, dtype=torch.int32, device=scores.device)
+    check(lib.hk_nts_nms(ptr(scores), ptr(anchors), ptr(index), ptr(boxes), b, a, topn, float(iou_thresh), stream()), 'hk_nts_nms')
+    return index.long(), boxes
+
+
+def nts_crop_resize(images, boxes, pad, size):
+    """images [B,C,H,W], boxes integer [B,N,4] = y0, x0, y1, x1 in image coordinates -> [B N,C,size_h,size_w]: each box
+    cut out of its image as if the image were zero-padded by `pad` on every side (the box is clipped to the padded
+    extent) and resized bilinearly with align_corners=True.  replaces F.pad and the double loop of F.interpolate,
+    NTSNet.py:31,43-47.  No autograd: the reference detaches the crops."""
+    if images.dim() != 4 or min(images.shape) < 1:
+        raise _lib.HawkeyeHipError(f'nts_crop_resize: images must be [B, C, H, W], got {tuple(images.shape)}')
+    images = _f32c(images.detach())
+    b, c, h, w = images.shape
+    if boxes.dim() != 3 or boxes.shape[1] < 1:
+        raise _lib.HawkeyeHipError(f'nts_crop_resize: boxes must be [B, N, 4], got {tuple(boxes.shape)}')
+    n = boxes.shape[1]
+    boxes = _nts_int(boxes, (b, n, 4), images.device, 'nts_crop_resize', 'boxes')
+    oh, ow = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    if oh < 1 or ow < 1 or int(pad) < 0:
+        raise _lib.HawkeyeHipError(f'nts_crop_resize: size {size} and pad {pad} must be positive / non-negative')
+    lib = _lib.load()
+    out = torch.empty(b * n, c, oh, ow, dtype=torch.float32, device=images.device)
+    check(lib.hk_nts_crop_resize(ptr(images), ptr(boxes), ptr(out), b, n, c, h, w, int(pad), oh, ow, stream()), 'hk_nts_crop_resize')
+    return out
+
+
+def _nts_loss_args(raw_logits, concat_logits, part_logits, top_n_prob, labels, what='nts_loss'):
+    if raw_logits.dim() != 2 or raw_logits.shape != concat_logits.shape:
+        raise _lib.HawkeyeHipError(f'{what}: raw and concat logits of shapes {tuple(raw_logits.shape)} and '
+                                   f'{tuple(concat_logits.shape)}; two [B, C] matrices of one shape are needed')
+    b, c = raw_logits.shape
+    if part_logits.dim() != 3 or part_logits.shape[0] != b or part_logits.shape[2] != c or part_logits.shape[1] < 1:
+        raise _lib.HawkeyeHipError(f'{what}: part_logits must be [{b}, N, {c}], got {tuple(part_logits.shape)}')
+    n = part_logits.shape[1]
+    if tuple(top_n_prob.shape) != (b, n):
+        raise _lib.HawkeyeHipError(f'{what}: top_n_prob must be [{b}, {n}], got {tuple(top_n_prob.shape)}')
+    for t in (concat_logits, part_logits, top_n_prob):
+        if t.device != raw_logits.device:
+            raise _lib.HawkeyeHipError(f'{what}: tensors on {raw_logits.device} and {t.device}')
+    if labels.is_floating_point() or labels.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'{what}: labels must be integers; got {labels.dtype}')
+    if tuple(labels.shape) != (b,):
+        raise _lib.HawkeyeHipError(f'{what}: {b} samples need labels of shape ({b},), got {tuple(labels.shape)}')
+    y = labels.to(device=raw_logits.device, dtype=torch.int32).contiguous()
+    return _f32c(raw_logits), _f32c(concat_logits), _f32c(part_logits), _f32c(top_n_prob), y
+
+
+class _NTSLoss(torch.autograd.Function):
+    """replaces NTSLoss.__call__, list_loss and ranking_loss, model/loss/NTS_loss.py:15-47.  The kernel returns the five
+    loss terms and all four gradients of the total in one launch; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, raw_logits, concat_logits, part_logits, top_n_prob, labels, label_smoothing):
+        raw, cat, part, prob, y = _nts_loss_args(raw_logits, concat_logits, part_logits, top_n_prob, labels)
+        lib = _lib.load()
+        b, n, c = part.shape
+        loss = torch.empty(5, dtype=torch.float32, device=raw.device)
+        grads = [torch.empty_like(t) for t in (raw, cat, part, prob)]
+        nws = lib.hk_nts_loss_ws_bytes(b, n, c)
+        ws = _ws(nws, raw.device)
+        check(lib.hk_nts_loss(ptr(raw), ptr(cat), ptr(part), ptr(prob), ptr(y), label_smoothing, ptr(loss), *[ptr(g) for g in grads],
+                              b, n, c, ptr(ws), nws, stream()), 'hk_nts_loss')
+        ctx.save_for_backward(*grads)
+        parts = loss[1:]
+        ctx.mark_non_differentiable(parts)
+        return loss[0], parts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        return tuple(t * g for t in ctx.saved_tensors) + (None, None)
+
+
+def nts_loss(raw_logits, concat_logits, part_logits, top_n_prob, labels, label_smoothing=0.1):
+    """NTS-Net's loss on raw_logits, concat_logits [B,C], part_logits [B,N,C], top_n_prob [B,N], labels [B] -> the scalar
+    raw CE + concat CE + part-class CE (label-smoothed means) + the ranking hinge over the proposals' scores gated by
+    their unsmoothed part losses.  part_logits receives gradient from the part-class CE only (the gate has none),
+    top_n_prob from the ranking term only."""
+    return _NTSLoss.apply(raw_logits, concat_logits, part_logits, top_n_prob, labels, float(label_smoothing))[0]
+
+
+def nts_loss_with_parts(raw_logits, concat_logits, part_logits, top_n_prob, labels, label_smoothing=0.1):
+    """nts_loss plus the device tensor [raw CE, concat CE, part-class CE, rank] (not differentiable)."""
+    return _NTSLoss.apply(raw_logits, concat_logits, part_logits, top_n_prob, labels, float(label_smoothing))
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

@@ -485,6 +485,38 @@ size_t hk_apinet_loss_ws_bytes(int R, int C);
 int hk_apinet_loss(const float* self_logits, const float* other_logits, const int32_t* labels, float smoothing, float margin,
                    float* loss, float* dself, float* dother, int R, int C, void* ws, size_t ws_bytes, hk_stream_t stream);
 
+/* ------------------------------------------------ NTS-Net head: proposal NMS, part crops, loss ----
+ * replaces model/methods/NTS_Net/NTSNet.py:29-47 with anchors.py:63-90 (all scores copied to the host, a numpy greedy NMS
+ * per image, a zero-padded copy of the batch, B x topN F.interpolate calls) and model/loss/NTS_loss.py:15-47 (an .item()
+ * per part row, a Python loop over the proposals).  Every entry point: no host synchronisation, no allocation
+ * (capturable in a hipGraph), no float atomics, fixed summation orders - the same bits on every run.
+ * HK_ERR_BAD_ARG: null pointer, a size <= 0, pad < 0, iou_thresh NaN, smoothing outside [0, 1];
+ * HK_ERR_UNSUPPORTED: A > 2048, B N > 65535 crops, B (N + 2) > 2^22 loss rows; HK_ERR_WORKSPACE: short workspace.
+ *   hk_nts_nms: scores [B,A] ; anchors int32 [A,4] = y0, x0, y1, x1 -> index int32 [B,topn], boxes int32 [B,topn,4].
+ *     hard_nms (anchors.py:63-90) per image: take the live anchor with the highest score, then keep a live anchor only if
+ *     its IoU with it is < iou_thresh, strictly; IoU from corner differences without + 1, the intersection 0 when a side
+ *     length is negative, evaluated in float64 as the reference evaluates it (0 / 0: suppressed).  Equal scores: the highest
+ *     index.  A NaN score counts as -inf.  A slot that no live anchor can fill repeats the last chosen anchor (the
+ *     reference returns a ragged array there); its `res.any()` stop is not reproduced.
+ *   hk_nts_crop_resize: images [B,C,H,W] ; boxes int32 [B,N,4] in image coordinates (they may reach outside) ->
+ *     out [B N,C,out_h,out_w]: the box clipped to [-pad, H + pad) x [-pad, W + pad), read from the image with zeros
+ *     outside it, resized bilinearly with align_corners (src = dst (len - 1) / (out - 1), 0 when out == 1); an empty box
+ *     gives zeros.  16-byte stores where out_w % 4 == 0 and out is 16-byte aligned.  No backward: the reference detaches.
+ *   hk_nts_loss: raw_logits, concat_logits [B,C] ; part_logits [B,N,C] ; top_n_prob [B,N] ; labels int32 [B] ->
+ *     loss [5] = total, raw CE, concat CE, part-class CE, rank ; draw, dconcat [B,C], dpart [B,N,C], dprob [B,N] = d total.
+ *     The three CEs are label-smoothed means over their rows; part_loss[b,j] = -log_softmax(part_logits[b,j])[y_b] ;
+ *     rank = (1 / B) sum_b sum_i sum_j relu(1 - s_bi + s_bj) [part_loss_bj > part_loss_bi] with s = top_n_prob; the
+ *     indicator carries no gradient.  A label outside [0, C) reads nothing and makes the loss NaN.
+ *     ws: hk_nts_loss_ws_bytes(B, N, C) (0 for sizes the call refuses). */
+int hk_nts_nms(const float* scores, const int32_t* anchors, int32_t* index, int32_t* boxes, int B, int A, int topn,
+               double iou_thresh, hk_stream_t stream);
+int hk_nts_crop_resize(const float* images, const int32_t* boxes, float* out, int B, int N, int C, int H, int W, int pad,
+                       int out_h, int out_w, hk_stream_t stream);
+size_t hk_nts_loss_ws_bytes(int B, int N, int C);
+int hk_nts_loss(const float* raw_logits, const float* concat_logits, const float* part_logits, const float* top_n_prob,
+                const int32_t* labels, float smoothing, float* loss, float* draw, float* dconcat, float* dpart, float* dprob,
+                int B, int N, int C, void* ws, size_t ws_bytes, hk_stream_t stream);
+
 /* ------------------------------------------------ CIN channel interaction (8f-2) ----
  * SCI: W = softmax_rows(-X X^T / HW), Y = W X ; CCI: Yc[b] = |W[b] - w_b W[(b + B/2) % B]| X[b].
  * replaces the bmm / softmax / abs / bmm parts of ChannelInteractionModule.forward,
