@@ -106,6 +106,12 @@ SIGNATURES = {
     'hk_nts_crop_resize': (c_i, [c_f, c_f, c_f] + [c_i] * 8 + [c_f]),
     'hk_nts_loss_ws_bytes': (c_sz, [c_i, c_i, c_i]),
     'hk_nts_loss': (c_i, [c_f] * 5 + [c_fl] + [c_f] * 5 + [c_i, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_crossx_me_fwd': (c_i, [c_f] * 7 + [c_i] * 5 + [c_f]),
+    'hk_crossx_me_bwd': (c_i, [c_f] * 12 + [c_i] * 5 + [c_f]),
+    'hk_crossx_up_add_fwd': (c_i, [c_f] * 3 + [c_i] * 6 + [c_f]),
+    'hk_crossx_up_add_bwd': (c_i, [c_f] * 2 + [c_i] * 6 + [c_f]),
+    'hk_crossx_loss_ws_bytes': (c_sz, [c_i] * 6),
+    'hk_crossx_loss': (c_i, [c_f] * 7 + [c_fl] * 4 + [c_f] * 7 + [c_i] * 6 + [c_f, c_sz, c_f]),
     'hk_cin_sci_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_sci_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_f]),
     'hk_cin_cci_fwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),

@@ -1172,6 +1172,191 @@ def nts_loss_with_parts(raw_logits, concat_logits, part_logits, top_n_prob, labe
     return _NTSLoss.apply(raw_logits, concat_logits, part_logits, top_n_prob, labels, float(label_smoothing))
 
 
+# --------------------------------------------------------------------- CrossX multi-excitation block, upsample + add, loss
+ME_POOLS = {'max': 0, 'avg': 1}
+
+
+def _cx_map(t, shape, what, name):
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.HawkeyeHipError(f'{what}: {name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    return _f32c(t)
+
+
+def crossx_me_bwd(d_main, d_parts, d_pooled, argmax, dz, out, gates, main, parts, pool):
+    """The raw backward of `crossx_me` (hk_crossx_me_bwd): d_main [N,C,H,W], d_parts [P,N,C,H,W], d_pooled [P,N,C] and
+    dz [N,C] - the gradient that reaches the squeeze GAP(out) - may each be None, meaning zero -> (d_out, d_res, d_gates).
+    No autograd."""
+    lib = _lib.load()
+    mode = ME_POOLS[pool]
+    p, n, c, h, w = parts.shape
+    out, main, parts, gates = _cx_map(out, (n, c, h, w), 'crossx_me_bwd', 'out'), _cx_map(main, (n, c, h, w), 'crossx_me_bwd', 'main'), \
+        _f32c(parts), _cx_map(gates, (p, n, c), 'crossx_me_bwd', 'gates')
+    d_main = None if d_main is None else _cx_map(d_main, (n, c, h, w), 'crossx_me_bwd', 'd_main')
+    d_parts = None if d_parts is None else _cx_map(d_parts, (p, n, c, h, w), 'crossx_me_bwd', 'd_parts')
+    d_pooled = None if d_pooled is None else _cx_map(d_pooled, (p, n, c), 'crossx_me_bwd', 'd_pooled')
+    dz = None if dz is None else _cx_map(dz, (n, c), 'crossx_me_bwd', 'dz')
+    d_out, d_res, d_gates = torch.empty_like(out), torch.empty_like(out), torch.empty_like(gates)
+    check(lib.hk_crossx_me_bwd(ptr(d_main), ptr(d_parts), ptr(d_pooled), ptr(argmax), ptr(dz), ptr(out), ptr(gates), ptr(main), ptr(parts),
+                               ptr(d_out), ptr(d_res), ptr(d_gates), p, n, c, h * w, mode, stream()), 'hk_crossx_me_bwd')
+    return d_out, d_res, d_gates
+
+
+class _CrossXME(torch.autograd.Function):
+    """replaces the tail of Bottleneck.forward with MELayer's multiplies (model/methods/CrossX.py:62-70,109-119) and the
+    adaptive pools of ResNet.forward (:225-226)."""
+
+    @staticmethod
+    def forward(ctx, out, res, gates, pool):
+        lib = _lib.load()
+        mode = ME_POOLS[pool]
+        out = _f32c(out)
+        if out.dim() != 4 or min(out.shape) < 1:
+            raise _lib.HawkeyeHipError(f'crossx_me: out must be [N, C, H, W], got {tuple(out.shape)}')
+        n, c, h, w = out.shape
+        res = _cx_map(res, (n, c, h, w), 'crossx_me', 'res')
+        if gates.dim() != 3 or tuple(gates.shape[1:]) != (n, c) or not 1 <= gates.shape[0] <= 3:
+            raise _lib.HawkeyeHipError(f'crossx_me: gates must be [P, N, C] = [1..3, {n}, {c}], got {tuple(gates.shape)}')
+        gates = _f32c(gates)
+        p = gates.shape[0]
+        main = torch.empty_like(out)
+        parts = torch.empty(p, n, c, h, w, dtype=torch.float32, device=out.device)
+        pooled = torch.empty(p, n, c, dtype=torch.float32, device=out.device)
+        argmax = torch.empty(p, n, c, dtype=torch.int32, device=out.device) if mode == 0 else None
+        check(lib.hk_crossx_me_fwd(ptr(out), ptr(res), ptr(gates), ptr(main), ptr(parts), ptr(pooled), ptr(argmax), p, n, c, h * w, mode,
+                                   stream()), 'hk_crossx_me_fwd')
+        ctx.pool = pool
+        ctx.save_for_backward(out, gates, main, parts, argmax)
+        ctx.set_materialize_grads(False)                   # an unused output costs no read of a map of zeros
+        return main, parts, pooled
+
+    @staticmethod
+    def backward(ctx, d_main, d_parts, d_pooled):
+        out, gates, main, parts, argmax = ctx.saved_tensors
+        return crossx_me_bwd(d_main, d_parts, d_pooled, argmax, None, out, gates, main, parts, ctx.pool) + (None,)
+
+
+def crossx_me(out, res, gates, pool):
+    """The end of a multi-excitation bottleneck in one pass: out, res [N,C,H,W] (the block's bn3 output and its residual),
+    gates [P,N,C] (after the sigmoid), pool 'max' or 'avg' -> main [N,C,H,W] = relu(out + res), parts [P,N,C,H,W] =
+    relu(out * gates[p] + res), pooled [P,N,C] = each part's spatial max (ties: the lowest index) or mean.  The backward
+    is one pass too; the pooled gradient is never a map."""
+    if pool not in ME_POOLS:
+        raise _lib.HawkeyeHipError(f"crossx_me: pool must be 'max' or 'avg', got {pool!r}")
+    return _CrossXME.apply(out, res, gates, pool)
+
+
+class _CrossXUpAdd(torch.autograd.Function):
+    """replaces F.interpolate(b, 28) + torch.add, model/methods/CrossX.py:213-223."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        lib = _lib.load()
+        a, b = _f32c(a), _f32c(b)
+        n, c, ho, wo = a.shape
+        hi, wi = b.shape[2:]
+        y = torch.empty_like(a)
+        check(lib.hk_crossx_up_add_fwd(ptr(a), ptr(b), ptr(y), n, c, hi, wi, ho, wo, stream()), 'hk_crossx_up_add_fwd')
+        ctx.dims = (n, c, hi, wi, ho, wo)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        n, c, hi, wi, ho, wo = ctx.dims
+        db = None
+        if ctx.needs_input_grad[1]:
+            g = _f32c(dy)
+            db = torch.empty(n, c, hi, wi, dtype=torch.float32, device=dy.device)
+            check(lib.hk_crossx_up_add_bwd(ptr(g), ptr(db), n, c, hi, wi, ho, wo, stream()), 'hk_crossx_up_add_bwd')
+        return dy, db                                      # a's gradient is the incoming one itself
+
+
+def crossx_up_add(a, b):
+    """a [N,C,Ho,Wo] + nearest_upsample(b [N,C,Hi,Wi]) with Ho % Hi == 0 and Wo % Wi == 0; the upsampled map is never
+    written."""
+    if a.dim() != 4 or b.dim() != 4 or tuple(a.shape[:2]) != tuple(b.shape[:2]) or min(a.shape) < 1 or min(b.shape) < 1:
+        raise _lib.HawkeyeHipError(f'crossx_up_add: two [N, C, H, W] maps of one N and C are needed, got {tuple(a.shape)} and {tuple(b.shape)}')
+    if a.shape[2] % b.shape[2] or a.shape[3] % b.shape[3]:
+        raise _lib.HawkeyeHipError(f'crossx_up_add: the size {tuple(a.shape[2:])} is no whole multiple of {tuple(b.shape[2:])}')
+    if a.device != b.device:
+        raise _lib.HawkeyeHipError(f'crossx_up_add: tensors on {a.device} and {b.device}')
+    return _CrossXUpAdd.apply(a, b)
+
+
+def _cx_features(feats, b, device, what, name):
+    """A list of P tensors [B,C,1,1] / [B,C], or one [P,B,C] tensor -> [P,B,C] dense."""
+    t = torch.stack([f.reshape(f.shape[0], -1) for f in feats]) if isinstance(feats, (list, tuple)) else feats
+    if t.dim() != 3 or t.shape[1] != b or not 1 <= t.shape[0] <= 3 or t.shape[2] < 1:
+        raise _lib.HawkeyeHipError(f'{what}: {name} must be 1 to 3 parts of [{b}, C] features, got {tuple(t.shape)}')
+    if t.device != device:
+        raise _lib.HawkeyeHipError(f'{what}: tensors on {device} and {t.device}')
+    return t
+
+
+class _CrossXLoss(torch.autograd.Function):
+    """replaces CrossXLoss.__call__ and RegularLoss.forward, model/loss/CrossX_loss.py:13-64: six loss terms and all six
+    gradients from one launch; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, ulti, plty, cmbn, f_ulti, f_plty, f_cmbn, labels, gamma):
+        lib = _lib.load()
+        ulti, plty, cmbn, f_ulti, f_plty, f_cmbn = (_f32c(t) for t in (ulti, plty, cmbn, f_ulti, f_plty, f_cmbn))
+        b, k = ulti.shape
+        p = f_ulti.shape[0]
+        cs = [f.shape[2] for f in (f_ulti, f_plty, f_cmbn)]
+        loss = torch.empty(6, dtype=torch.float32, device=ulti.device)
+        grads = [torch.empty_like(t) for t in (ulti, plty, cmbn, f_ulti, f_plty, f_cmbn)]
+        nws = lib.hk_crossx_loss_ws_bytes(b, k, p, *cs)
+        ws = _ws(nws, ulti.device)
+        check(lib.hk_crossx_loss(ptr(ulti), ptr(plty), ptr(cmbn), ptr(labels), ptr(f_ulti), ptr(f_plty), ptr(f_cmbn), gamma[0], gamma[1],
+                                 gamma[2], 1.0, ptr(loss), *[ptr(g) for g in grads], b, k, p, *cs, ptr(ws), nws, stream()), 'hk_crossx_loss')
+        ctx.save_for_backward(*grads)
+        terms = loss[1:]
+        ctx.mark_non_differentiable(terms)
+        return loss[0], terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        return tuple(t * g for t in ctx.saved_tensors) + (None, None)
+
+
+def _crossx_loss_args(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma, what='crossx_loss'):
+    if ulti.dim() != 2 or ulti.shape != plty.shape or ulti.shape != cmbn.shape:
+        raise _lib.HawkeyeHipError(f'{what}: three [B, K] logit matrices of one shape are needed, got {tuple(ulti.shape)}, '
+                                   f'{tuple(plty.shape)} and {tuple(cmbn.shape)}')
+    b = ulti.shape[0]
+    if b < 2:                                              # the reference's squeeze() drops the batch axis at B = 1 and fails
+        raise _lib.HawkeyeHipError(f'{what}: the batch must hold at least 2 samples, got {b}')
+    for t in (plty, cmbn):
+        if t.device != ulti.device:
+            raise _lib.HawkeyeHipError(f'{what}: tensors on {ulti.device} and {t.device}')
+    feats = [_cx_features(f, b, ulti.device, what, n) for f, n in ((ulti_ftrs, 'ulti_ftrs'), (plty_ftrs, 'plty_ftrs'), (cmbn_ftrs, 'cmbn_ftrs'))]
+    if len({f.shape[0] for f in feats}) != 1:
+        raise _lib.HawkeyeHipError(f'{what}: the three feature lists hold {[f.shape[0] for f in feats]} parts')
+    if labels.is_floating_point() or labels.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'{what}: labels must be integers; got {labels.dtype}')
+    if tuple(labels.shape) != (b,):
+        raise _lib.HawkeyeHipError(f'{what}: {b} samples need labels of shape ({b},), got {tuple(labels.shape)}')
+    gamma = tuple(float(v) for v in gamma)
+    if len(gamma) != 3:
+        raise _lib.HawkeyeHipError(f'{what}: gamma must hold three values (ulti, plty, cmbn), got {gamma}')
+    return feats, labels.to(device=ulti.device, dtype=torch.int64).contiguous(), gamma
+
+
+def crossx_loss_with_terms(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma):
+    """CrossX's loss on the three logit matrices [B,K], the three feature lists (P tensors [B,C,1,1] or [B,C] each, or one
+    [P,B,C] tensor; the width may differ per list) and labels [B] -> (total, the device tensor [cls, kl, reg_ulti, reg_plty,
+    reg_cmbn], not differentiable).  cls: the label-smoothed (0.1) cross entropy of the summed logits; kl: KL(softmax(ulti) |
+    softmax(plty)) + KL(softmax(ulti) | softmax(cmbn)) over B, the target carrying gradient too; reg: gamma x the upper
+    triangle of each list's part-correlation matrix."""
+    feats, y, gamma = _crossx_loss_args(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma)
+    return _CrossXLoss.apply(ulti, plty, cmbn, *feats, y, gamma)
+
+
+def crossx_loss(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma):
+    return crossx_loss_with_terms(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma)[0]
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

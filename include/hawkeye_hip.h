@@ -517,6 +517,50 @@ int hk_nts_loss(const float* raw_logits, const float* concat_logits, const float
                 const int32_t* labels, float smoothing, float* loss, float* draw, float* dconcat, float* dpart, float* dprob,
                 int B, int N, int C, void* ws, size_t ws_bytes, hk_stream_t stream);
 
+/* ------------------------------------------------ CrossX head: multi-excitation block, upsample + add, loss ----
+ * replaces model/methods/CrossX.py:109-119, :213-226 (a clone, P broadcast multiplies, P + 1 adds, P + 1 ReLUs, P pools and
+ * a nearest-upsampled map per part as separate passes) and model/loss/CrossX_loss.py:15-64 (a P x P correlation matrix
+ * filled on the host: 3 P^2 device-to-host copies).  Every entry point: no host synchronisation, no allocation (capturable
+ * in a hipGraph), no float atomics, fixed summation orders - the same bits on every run, whatever the alignment.
+ * HK_ERR_BAD_ARG: a null pointer that is not optional, a size <= 0, a mode other than 0 / 1; HK_ERR_UNSUPPORTED: P outside
+ * [1, 3], sizes past the index range, an output size that is no multiple of the input's (up_add), B < 2 (loss).
+ *   hk_crossx_me_fwd: out, res [N,C,HW] (the bottleneck's bn3 output and its residual) ; gates [P,N,C] (after the sigmoid)
+ *     -> main_out [N,C,HW] = max(out + res, 0) ; parts [P,N,C,HW] = max(out * gates[p] + res, 0) (the product rounded, then
+ *     the sum: no fma) ; pooled [P,N,C] = each part's spatial max (mode 0) or mean (mode 1) ; argmax int32 [P,N,C] (mode 0;
+ *     may be NULL in mode 1): the lowest index of the maximum, as AdaptiveMaxPool2d.  HW is arbitrary; 16-byte accesses
+ *     where HW % 4 == 0 and out, res, main_out and parts are 16-byte aligned.
+ *   hk_crossx_me_bwd: d_main [N,C,HW], d_parts [P,N,C,HW], d_pooled [P,N,C], dz [N,C] (the gradient that reaches the
+ *     squeeze GAP(out)) - each may be NULL, meaning zero - and the saved out, gates, main_out, parts, argmax ->
+ *     g_p = [parts_p > 0] (d_parts_p + the pooled backward of d_pooled_p: d_pooled / HW everywhere (mode 1), d_pooled at the
+ *     arg-max (mode 0); never a map) ;
+ *     d_out = [main > 0] d_main + sum_p gates_p g_p + dz / HW ; d_res = [main > 0] d_main + sum_p g_p ;
+ *     d_gates [P,N,C] = sum_hw g_p out.
+ *   hk_crossx_up_add_fwd: y [N,C,Ho,Wo] = a + nearest_upsample(b [N,C,Hi,Wi]), Ho % Hi == 0 and Wo % Wi == 0 (source pixel
+ *     = destination / factor, what F.interpolate(mode='nearest') takes for whole factors).
+ *   hk_crossx_up_add_bwd: db [N,C,Hi,Wi] = the sum of dy over each source pixel's children (rows, then columns); the
+ *     gradient of `a` is dy itself.
+ *   hk_crossx_loss: ulti, plty, cmbn [B,K] ; labels int64 [B] ; f_ulti [P,B,C_ulti], f_plty [P,B,C_plty], f_cmbn [P,B,C_cmbn] ->
+ *     loss [6] = total, cls, kl, reg_ulti, reg_plty, reg_cmbn ; d_* [B,K] and df_* (the features' shapes) = weight x d total.
+ *     cls: the label-smoothed (0.1) cross entropy of ulti + plty + cmbn, mean over B ;
+ *     kl = [KL(softmax(ulti) | softmax(plty)) + KL(softmax(ulti) | softmax(cmbn))] / B, with gradient into ulti through the
+ *     target as well ; reg_l = gamma_l [sum_i (1 - |s_i|^2 / B^2) + sum_{i<j} s_i . s_j / B^2], s_i = sum_b x_i[b] / |x_i[b]| ;
+ *     total = reg_ulti + reg_plty + reg_cmbn + kl + cls.  A zero feature row gives NaN; a label outside [0, K) reads
+ *     nothing and makes cls and total NaN.  ws: hk_crossx_loss_ws_bytes(B, K, P, C_ulti, C_plty, C_cmbn) (0 for sizes the
+ *     call refuses). */
+int hk_crossx_me_fwd(const float* out, const float* res, const float* gates, float* main_out, float* parts, float* pooled,
+                     int32_t* argmax, int P, int N, int C, int HW, int mode, hk_stream_t stream);
+int hk_crossx_me_bwd(const float* d_main, const float* d_parts, const float* d_pooled, const int32_t* argmax, const float* dz,
+                     const float* out, const float* gates, const float* main_saved, const float* parts, float* d_out,
+                     float* d_res, float* d_gates, int P, int N, int C, int HW, int mode, hk_stream_t stream);
+int hk_crossx_up_add_fwd(const float* a, const float* b, float* y, int N, int C, int Hi, int Wi, int Ho, int Wo,
+                         hk_stream_t stream);
+int hk_crossx_up_add_bwd(const float* dy, float* db, int N, int C, int Hi, int Wi, int Ho, int Wo, hk_stream_t stream);
+size_t hk_crossx_loss_ws_bytes(int B, int K, int P, int C_ulti, int C_plty, int C_cmbn);
+int hk_crossx_loss(const float* ulti, const float* plty, const float* cmbn, const int64_t* labels, const float* f_ulti,
+                   const float* f_plty, const float* f_cmbn, float gamma_ulti, float gamma_plty, float gamma_cmbn, float weight,
+                   float* loss, float* d_ulti, float* d_plty, float* d_cmbn, float* df_ulti, float* df_plty, float* df_cmbn, int B,
+                   int K, int P, int C_ulti, int C_plty, int C_cmbn, void* ws, size_t ws_bytes, hk_stream_t stream);
+
 /* ------------------------------------------------ CIN channel interaction (8f-2) ----
  * SCI: W = softmax_rows(-X X^T / HW), Y = W X ; CCI: Yc[b] = |W[b] - w_b W[(b + B/2) % B]| X[b].
  * replaces the bmm / softmax / abs / bmm parts of ChannelInteractionModule.forward,
