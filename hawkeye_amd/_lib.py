@@ -19,7 +19,7 @@ c_sz = ctypes.c_size_t
 c_ll = ctypes.c_longlong
 c_fl = ctypes.c_float
 
-# name -> (restype, argtypes); mirrors include/hawkeye_hip.h one to one
+# name -> (restype, argtypes); mirrors include/hawkeye_hip.h one to one (include/hawkeye_dcl.h: PLUGIN_SIGNATURES below)
 SIGNATURES = {
     'hk_version': (ctypes.c_char_p, []),
     'hk_tuning_set': (c_i, [ctypes.c_char_p, c_i]),
@@ -122,6 +122,29 @@ SIGNATURES = {
                            c_fl, c_fl, c_fl, c_f]),
 }
 
+# the entry points of include/hawkeye_dcl.h (plugins added after the table above was closed; same conventions)
+PLUGIN_SIGNATURES = {
+    'hk_dcl_head_fwd_ws_bytes': (c_sz, [c_i] * 4),
+    'hk_dcl_head_fwd': (c_i, [c_f] * 5 + [c_i] * 4 + [c_f, c_sz, c_f]),
+    'hk_dcl_head_bwd_ws_bytes': (c_sz, [c_i] * 4),
+    'hk_dcl_head_bwd': (c_i, [c_f] * 8 + [c_i] * 4 + [c_f, c_sz, c_f]),
+    'hk_dcl_loss': (c_i, [c_f] * 6 + [c_fl] * 5 + [c_f] * 4 + [c_i] * 4 + [c_f]),
+    'hk_dcl_swap_law': (c_i, [c_f] * 6 + [c_i] * 5 + [c_f]),
+}
+
+
+def bind(lib):
+    """Attach the prototypes of PLUGIN_SIGNATURES to a loaded library (the gfx950 build, or whatever stands in for it);
+    done once per library object.  Returns the library."""
+    if not getattr(lib, '_hk_plugins_bound', False):
+        for name, (res, args) in PLUGIN_SIGNATURES.items():
+            fn = getattr(lib, name)   # AttributeError => header/library drifted apart
+            fn.restype = res
+            fn.argtypes = args
+        lib._hk_plugins_bound = True
+    return lib
+
+
 _lib = None
 
 
@@ -146,7 +169,7 @@ def load():
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args
-    _lib = lib
+    _lib = bind(lib)
     return lib
 
 

@@ -1357,6 +1357,175 @@ def crossx_loss(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma
     return crossx_loss_with_terms(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma)[0]
 
 
+# --------------------------------------------------------------------- DCL head, loss and swap law
+def _dcl_head_args(x, weight, bias, what):
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise _lib.HawkeyeHipError(f'{what}: x must be [B, C, H, W], got {tuple(x.shape)}')
+    b, c, h, w = x.shape
+    if h < 2 or w < 2:                                     # the reference's AvgPool2d(2) has no output there and fails
+        raise _lib.HawkeyeHipError(f'{what}: the map must be at least 2 x 2, got {h} x {w}')
+    if weight.numel() != c:
+        raise _lib.HawkeyeHipError(f'{what}: weight must hold {c} values ([1, {c}, 1, 1] or [{c}]), got {tuple(weight.shape)}')
+    if bias.numel() != 1:
+        raise _lib.HawkeyeHipError(f'{what}: bias must hold one value, got {tuple(bias.shape)}')
+    for t in (weight, bias):
+        if t.device != x.device:
+            raise _lib.HawkeyeHipError(f'{what}: tensors on {x.device} and {t.device}')
+    return _f32c(x), _f32c(weight).reshape(c), _f32c(bias).reshape(1)
+
+
+def dcl_head_bwd(x, weight, mask, d_pooled, d_mask, need=(True, True, True)):
+    """The raw backward of `dcl_head` (hk_dcl_head_bwd): x [B,C,H,W], weight [C], the saved mask [B,M]; d_pooled [B,C] and
+    d_mask [B,M] may each be None, meaning zero -> (dx, dw [C], dbias [1]), None where `need` says so.  No autograd."""
+    lib = _lib.bind(_lib.load())
+    x, weight, mask = _f32c(x), _f32c(weight).reshape(-1), _f32c(mask)
+    b, c, h, w = x.shape
+    m = (h // 2) * (w // 2)
+    if tuple(mask.shape) != (b, m):
+        raise _lib.HawkeyeHipError(f'dcl_head_bwd: mask must have the shape {(b, m)}, got {tuple(mask.shape)}')
+    d_pooled = None if d_pooled is None else _cx_map(d_pooled, (b, c), 'dcl_head_bwd', 'd_pooled')
+    d_mask = None if d_mask is None else _cx_map(d_mask, (b, m), 'dcl_head_bwd', 'd_mask')
+    dx = torch.empty_like(x) if need[0] else None
+    dw = torch.empty(c, dtype=torch.float32, device=x.device) if need[1] else None
+    dbias = torch.empty(1, dtype=torch.float32, device=x.device) if need[2] else None
+    nws = lib.hk_dcl_head_bwd_ws_bytes(b, c, h, w)
+    ws = _ws(nws, x.device)
+    check(lib.hk_dcl_head_bwd(ptr(x), ptr(weight), ptr(mask), ptr(d_pooled), ptr(d_mask), ptr(dx), ptr(dw), ptr(dbias), b, c, h, w, ptr(ws),
+                              nws, stream()), 'hk_dcl_head_bwd')
+    return dx, dw, dbias
+
+
+class _DCLHead(torch.autograd.Function):
+    """replaces Convmask, avgpool2, tanh, the view and avgpool of DCL.forward, model/methods/DCL.py:33-39."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        lib = _lib.bind(_lib.load())
+        ctx.wshape, ctx.bshape = weight.shape, bias.shape
+        x, weight, bias = _dcl_head_args(x, weight, bias, 'dcl_head')
+        b, c, h, w = x.shape
+        pooled = torch.empty(b, c, dtype=torch.float32, device=x.device)
+        mask = torch.empty(b, (h // 2) * (w // 2), dtype=torch.float32, device=x.device)
+        nws = lib.hk_dcl_head_fwd_ws_bytes(b, c, h, w)
+        ws = _ws(nws, x.device)
+        check(lib.hk_dcl_head_fwd(ptr(x), ptr(weight), ptr(bias), ptr(pooled), ptr(mask), b, c, h, w, ptr(ws), nws, stream()),
+              'hk_dcl_head_fwd')
+        ctx.save_for_backward(x, weight, mask)
+        ctx.set_materialize_grads(False)                   # an unused output reaches the kernel as a null gradient
+        return pooled, mask
+
+    @staticmethod
+    def backward(ctx, d_pooled, d_mask):
+        x, weight, mask = ctx.saved_tensors
+        dx, dw, dbias = dcl_head_bwd(x, weight, mask, d_pooled, d_mask, ctx.needs_input_grad)
+        return dx, None if dw is None else dw.view(ctx.wshape), None if dbias is None else dbias.view(ctx.bshape)
+
+
+def dcl_head(x, weight, bias):
+    """DCL's two readers of the last map in one read: x [B,C,H,W], weight [1,C,1,1] or [C] and bias [1] (Convmask's) ->
+    pooled [B,C] = the spatial mean, mask [B,(H/2)(W/2)] = tanh(avgpool2x2(sum_c weight[c] x[:,c] + bias)).  One autograd
+    node; its backward reads x once and writes dx once."""
+    return _DCLHead.apply(x, weight, bias)
+
+
+class _DCLLoss(torch.autograd.Function):
+    """replaces DCLLoss.__call__, model/loss/DCL_loss.py:16-21: the four loss terms and the three gradients from one
+    launch; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, logits, swap_logits, mask, labels, labels_swap, law, coef, smoothing):
+        lib = _lib.bind(_lib.load())
+        logits, swap_logits, mask = _f32c(logits), _f32c(swap_logits), _f32c(mask)
+        n, k = logits.shape
+        loss = torch.empty(4, dtype=torch.float32, device=logits.device)
+        grads = [torch.empty_like(t) for t in (logits, swap_logits, mask)]
+        check(lib.hk_dcl_loss(ptr(logits), ptr(swap_logits), ptr(mask), ptr(labels), ptr(labels_swap), ptr(law), coef[0], coef[1], coef[2],
+                              smoothing, 1.0, ptr(loss), *[ptr(g) for g in grads], n, k, swap_logits.shape[1], mask.shape[1], stream()),
+              'hk_dcl_loss')
+        ctx.save_for_backward(*grads)
+        terms = loss[1:]
+        ctx.mark_non_differentiable(terms)
+        return loss[0], terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        return tuple(t * g for t in ctx.saved_tensors) + (None,) * 5
+
+
+def _dcl_loss_args(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha, beta, gamma, what='dcl_loss'):
+    if logits.dim() != 2 or swap_logits.dim() != 2 or mask.dim() != 2 or min(logits.shape) < 1 or min(swap_logits.shape) < 1 or \
+            min(mask.shape) < 1 or not logits.shape[0] == swap_logits.shape[0] == mask.shape[0]:
+        raise _lib.HawkeyeHipError(f'{what}: logits [N, K], swap logits [N, S] and a mask [N, M] of one N are needed, got '
+                                   f'{tuple(logits.shape)}, {tuple(swap_logits.shape)} and {tuple(mask.shape)}')
+    n = logits.shape[0]
+    for t in (swap_logits, mask):
+        if t.device != logits.device:
+            raise _lib.HawkeyeHipError(f'{what}: tensors on {logits.device} and {t.device}')
+    for name, y in (('labels', labels), ('labels_swap', labels_swap)):
+        if y.is_floating_point() or y.dtype == torch.bool:
+            raise _lib.HawkeyeHipError(f'{what}: {name} must be integers; got {y.dtype}')
+        if tuple(y.shape) != (n,):
+            raise _lib.HawkeyeHipError(f'{what}: {n} samples need {name} of shape ({n},), got {tuple(y.shape)}')
+    if tuple(swap_law.shape) != tuple(mask.shape):
+        raise _lib.HawkeyeHipError(f'{what}: swap_law must have the mask\'s shape {tuple(mask.shape)}, got {tuple(swap_law.shape)}')
+    if not swap_law.is_floating_point():
+        raise _lib.HawkeyeHipError(f'{what}: swap_law must be floating point; got {swap_law.dtype}')
+    dev = logits.device
+    return (labels.to(device=dev, dtype=torch.int64).contiguous(), labels_swap.to(device=dev, dtype=torch.int64).contiguous(),
+            swap_law.to(device=dev, dtype=torch.float32).contiguous(), (float(alpha), float(beta), float(gamma)))
+
+
+def dcl_loss_with_terms(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha=1.0, beta=1.0, gamma=1.0, label_smoothing=0.1):
+    """DCL's loss on the class logits [N,K], the swap logits [N,S], the mask [N,M], labels and labels_swap [N] and the swap
+    law [N,M] -> (total, the device tensor [ce, swap, law], not differentiable).  ce, swap: label-smoothed cross entropies;
+    law: mean |mask - swap_law| (its gradient exactly 0 where they are equal); total = alpha ce + beta swap + gamma law."""
+    y, ys, law, coef = _dcl_loss_args(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha, beta, gamma)
+    return _DCLLoss.apply(logits, swap_logits, mask, y, ys, law, coef, float(label_smoothing))
+
+
+def dcl_loss(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha=1.0, beta=1.0, gamma=1.0, label_smoothing=0.1):
+    return dcl_loss_with_terms(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha, beta, gamma, label_smoothing)[0]
+
+
+_DCL_BOUNDS = {}
+
+
+def _dcl_bounds(h, w, gx, gy, device):
+    from .transforms import patch_bounds                   # the reference's crop_image bounds, in Python floats
+    key = (h, w, gx, gy, str(device))
+    if key not in _DCL_BOUNDS:                             # made once per shape; the upload is the only copy
+        _DCL_BOUNDS[key] = tuple(torch.tensor(patch_bounds(s, g), dtype=torch.int32).to(device) for s, g in ((w, gx), (h, gy)))
+    return _DCL_BOUNDS[key]
+
+
+def dcl_swap_law(u8_unswap, u8_swap, grid=(7, 7)):
+    """The swap law of DCL's data pipeline on the device: two uint8 batches [N,H,W,3] (an image and its patch-shuffled
+    version) and grid = (columns, rows) -> (law float32 [N, columns rows], index int32 of the same shape).  For each patch
+    of the swapped image (row-major) `index` names the patch of the unswapped image with the nearest sum of band means -
+    every decision as the reference takes it in float64, the lowest index on ties - and law = (index - P // 2) / P.  No
+    gradient."""
+    lib = _lib.bind(_lib.load())
+    gx, gy = (int(g) for g in grid)
+    for name, t in (('u8_unswap', u8_unswap), ('u8_swap', u8_swap)):
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
+            raise _lib.HawkeyeHipError(f'dcl_swap_law: {name} must be uint8 [N, H, W, 3], got {t.dtype} {tuple(t.shape)}')
+    if u8_unswap.shape != u8_swap.shape:
+        raise _lib.HawkeyeHipError(f'dcl_swap_law: two batches of one shape are needed, got {tuple(u8_unswap.shape)} and {tuple(u8_swap.shape)}')
+    if u8_unswap.device != u8_swap.device:
+        raise _lib.HawkeyeHipError(f'dcl_swap_law: tensors on {u8_unswap.device} and {u8_swap.device}')
+    n, h, w, _ = u8_unswap.shape
+    if gx < 1 or gy < 1:
+        raise _lib.HawkeyeHipError(f'dcl_swap_law: grid must hold two positive counts, got {grid}')
+    if w < gx or h < gy:                                   # the reference divides by the pixel count of an empty patch
+        raise _lib.HawkeyeHipError(f'dcl_swap_law: a {h} x {w} image has no {gy} x {gx} patches: a patch would be empty')
+    a, s = u8_unswap.contiguous(), u8_swap.contiguous()
+    bx, by = _dcl_bounds(h, w, gx, gy, a.device)
+    index = torch.empty(n, gx * gy, dtype=torch.int32, device=a.device)
+    law = torch.empty(n, gx * gy, dtype=torch.float32, device=a.device)
+    check(lib.hk_dcl_swap_law(ptr(a), ptr(s), ptr(bx), ptr(by), ptr(index), ptr(law), n, h, w, gx, gy, stream()), 'hk_dcl_swap_law')
+    return law, index
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

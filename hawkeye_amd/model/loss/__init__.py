@@ -4,3 +4,4 @@ from .peer_learning_loss import PeerLearningLoss  # noqa: F401
 from .APINet_loss import APINetLoss  # noqa: F401
 from .NTS_loss import NTSLoss  # noqa: F401
 from .CrossX_loss import CrossXLoss  # noqa: F401
+from .DCL_loss import DCLLoss  # noqa: F401

@@ -227,3 +227,69 @@ class ClassificationPresetEval:
         if self.device_finalize:
             return {'u8': torch.from_numpy(np.array(img, dtype=np.uint8)), 'erase': torch.zeros(4, dtype=torch.int32)}
         return normalize(to_float_tensor(img), self.mean, self.std)
+
+
+# --------------------------------------------------------------------------- DCL's jigsaw swap
+SWAP_WINDOW = 2          # neighbours that may change places: a patch moves by at most one step per shuffle
+SWAP_BORDER = 10         # pixels cut from every side before the image is taken apart
+
+
+def patch_bounds(size, parts):
+    """The cuts of a side of `size` pixels into `parts` patches, as the reference's crop_image makes them
+    (dataset/dataset_DCL.py:86-87, dataset/transforms.py:262-263): int((size / parts) * i) in Python floats."""
+    return [int((size / parts) * i) for i in range(parts + 1)]
+
+
+def _shuffle_tail(seq, rng):
+    """Shuffles the last SWAP_WINDOW entries of `seq` among themselves (one entry: nothing is drawn)."""
+    lo = max(len(seq) - SWAP_WINDOW, 0)
+    tail = seq[lo:]
+    rng.shuffle(tail)
+    seq[lo:] = tail
+
+
+def swap_permutation(grid, rng=random):
+    """The reference's windowed shuffle (dataset/transforms.py:276-300) on patch numbers: grid = (columns, rows) -> a list
+    whose entry k is the row-major number of the source patch that lands at row-major position k.  The patches are dealt
+    out in order; after each one the last two of the open row are shuffled, a full row joins the finished rows, and the
+    last two finished rows are shuffled - after every patch, not only at a row's end.  Draws from `rng` exactly as the
+    reference draws from `random`: one `shuffle` of a two-element list per step that has two elements to shuffle."""
+    gx, gy = int(grid[0]), int(grid[1])
+    rows, row = [], []
+    for number in range(gx * gy):
+        row.append(number)
+        _shuffle_tail(row, rng)
+        if len(row) == gx:
+            rows.append(row)
+            row = []
+        if rows:
+            _shuffle_tail(rows, rng)
+    return [number for r in rows for number in r]
+
+
+class RandomSwap:
+    """DCL's destruction step (dataset/transforms.py:243-319): cut SWAP_BORDER pixels from every side, take the rest
+    apart into size[0] x size[1] patches (columns x rows), move them by `swap_permutation`, resize each to the common
+    patch size with Image.LANCZOS (the filter ANTIALIAS named), paste them side by side and resize the result back to the
+    input's size with PIL's default filter."""
+
+    def __init__(self, size):
+        self.size = (int(size), int(size)) if isinstance(size, (int, float)) else (int(size[0]), int(size[1]))
+        if not isinstance(size, (int, float)) and len(size) != 2:
+            raise ValueError(f'RandomSwap: size must be one number or (columns, rows), got {size}')
+
+    def __repr__(self):
+        return f'{type(self).__name__}(size={self.size})'
+
+    def __call__(self, img, rng=random):
+        gx, gy = self.size
+        width, height = img.size
+        inner = img.crop((SWAP_BORDER, SWAP_BORDER, width - SWAP_BORDER, height - SWAP_BORDER))
+        w, h = inner.size
+        xs, ys = patch_bounds(w, gx), patch_bounds(h, gy)
+        patches = [inner.crop((xs[i], ys[j], min(xs[i + 1], w), min(ys[j + 1], h))) for j in range(gy) for i in range(gx)]
+        pw, ph = int(w / gx), int(h / gy)
+        canvas = Image.new('RGB', (pw * gx, ph * gy))
+        for k, source in enumerate(swap_permutation(self.size, rng)):
+            canvas.paste(patches[source].resize((pw, ph), Image.LANCZOS), ((k % gx) * pw, (k // gx) * ph))
+        return canvas.resize((width, height))

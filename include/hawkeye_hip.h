@@ -606,4 +606,9 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 #ifdef __cplusplus
 }
 #endif
+
+/* The entry points of plugins added after the table above was closed live in headers of their own (bound by the
+ * PLUGIN_SIGNATURES table of hawkeye_amd/_lib.py); including this header still gives the whole C ABI. */
+#include "hawkeye_dcl.h"
+
 #endif /* HAWKEYE_HIP_H */

@@ -1,0 +1,356 @@
+"""DCL, host side: opt-in registration, the constructor's behaviour for the four cls_2 / cls_2xmul settings and the
+state_dict against the reference's key lists, swap_permutation and RandomSwap against what the reference's RandomSwap
+drew and made under a fixed random.seed, both collate functions against stored outputs of the reference's, the datasets,
+the functional wrappers' refusals, the synthetic yaml, the trainer's optimizer and scheduler, DCLLoss and DCL.forward on
+the emulated library against the goldens, and the golden tool's --check.  No GPU."""
+import importlib
+import json
+import os
+import random
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import hawkeye_amd.model  # noqa: F401
+from hawkeye_amd.config import CfgNode
+from hawkeye_amd.model.registry import MODEL, install_into
+from hawkeye_amd.utils.repository import Repository
+
+import dcl_inputs as T
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+KEYS = json.load(open(os.path.join(HERE, 'golden', 'dcl_state_dict.json')))
+GOLDEN = T.load()
+PLUGIN_MODULES = ('hawkeye_amd.model.methods.DCL', 'hawkeye_amd.examples.DCL')
+
+
+def forget_plugin():
+    MODEL.pop('DCL', None)
+    for name in PLUGIN_MODULES:
+        sys.modules.pop(name, None)
+
+
+@pytest.fixture
+def plugin():
+    """The opt-in import, undone afterwards: the registry other tests see holds the default plugins only."""
+    assert 'DCL' not in MODEL
+    yield importlib.import_module(PLUGIN_MODULES[0])
+    forget_plugin()
+
+
+def config(cls_2=True, cls_2xmul=False, **kw):
+    return CfgNode(dict(name='DCL', num_classes=T.CLASSES, cls_2=cls_2, cls_2xmul=cls_2xmul, pretrained=False, **kw))
+
+
+def test_absent_from_the_default_registry_and_registered_by_the_import():
+    default = ['APCNN', 'BCNN', 'CBCNN', 'CIN', 'MPN', 'OSMENet', 'ResNet101', 'ResNet50']       # what tests/test_models_cpu.py pins
+    assert sorted(MODEL) == default and sorted(install_into(Repository())) == default
+    mod = importlib.import_module(PLUGIN_MODULES[0])
+    try:
+        assert sorted(MODEL) == sorted(default + ['DCL']) and MODEL.get('DCL') is mod.DCL
+        ref = Repository()
+        install_into(ref)
+        assert ref['DCL'] is mod.DCL
+    finally:
+        forget_plugin()
+    assert sorted(MODEL) == default
+
+
+@pytest.mark.parametrize('cls_2', [False, True])
+@pytest.mark.parametrize('cls_2xmul', [False, True])
+def test_constructor_state_dict_and_attributes_are_the_reference_ones(plugin, cls_2, cls_2xmul):
+    net = plugin.DCL(config(cls_2, cls_2xmul))
+    want = KEYS[f'{int(cls_2)}{int(cls_2xmul)}']
+    assert [[k, list(v.shape)] for k, v in net.state_dict().items()] == want['state_dict']
+    assert [n for n, _ in net.named_children()] == want['children']
+    assert sum(p.numel() for p in net.parameters()) == want['n_params']
+    assert (net.num_classes, net.cls_2, net.cls_2xmul) == (T.CLASSES, cls_2, cls_2xmul)
+    assert isinstance(net.backbone, torch.nn.Sequential) and len(net.backbone) == 8
+    assert isinstance(net.Convmask, torch.nn.Conv2d) and tuple(net.Convmask.weight.shape) == (1, 2048, 1, 1) and net.Convmask.bias.shape == (1,)
+    assert isinstance(net.avgpool2, torch.nn.AvgPool2d) and isinstance(net.avgpool, torch.nn.AdaptiveAvgPool2d)
+    assert tuple(net.classifier.weight.shape) == (T.CLASSES, 2048) and net.classifier.bias is None
+    if cls_2xmul:                                           # the 2 K classifier wins when both are set
+        assert tuple(net.classifier_swap.weight.shape) == (2 * T.CLASSES, 2048)
+    elif cls_2:
+        assert tuple(net.classifier_swap.weight.shape) == (2, 2048)
+    else:                                                   # the reference has no swap classifier then, and its forward fails
+        assert not hasattr(net, 'classifier_swap')
+        with pytest.raises(AttributeError, match='classifier_swap'):
+            net(torch.zeros(1, 3, 64, 64))
+
+
+def test_pretrained_is_read_from_the_config_and_defaults_to_true(plugin, monkeypatch):
+    asked = []
+    real = plugin.resnet50
+    monkeypatch.setattr(plugin, 'resnet50', lambda pretrained=False, **kw: asked.append(pretrained) or real(pretrained=False, **kw))
+    plugin.DCL(CfgNode(dict(num_classes=3, cls_2=True, cls_2xmul=False)))
+    plugin.DCL(config(pretrained_unused=1))
+    assert asked == [True, False]
+
+
+def test_swap_permutation_draws_what_the_reference_drew():
+    from hawkeye_amd.transforms import swap_permutation
+    random.seed(T.SWAP_SEED)
+    assert swap_permutation((7, 7)) == GOLDEN['swap_perm'].tolist()
+    after = random.random()
+    random.seed(T.SWAP_SEED)
+    own = random.Random(T.SWAP_SEED)
+    assert swap_permutation((7, 7), own) == GOLDEN['swap_perm'].tolist() and own.random() == after      # the same consumption
+    assert sorted(swap_permutation((3, 5))) == list(range(15)) and swap_permutation((1, 1)) == [0]
+
+
+def test_random_swap_makes_the_reference_image():
+    import PIL
+    from PIL import Image
+    from hawkeye_amd.transforms import RandomSwap
+    swap = RandomSwap((7, 7))
+    assert swap.size == (7, 7) and RandomSwap(3).size == (3, 3) and 'size=(7, 7)' in repr(swap)
+    random.seed(T.SWAP_SEED)
+    probe = np.array(swap(Image.fromarray(T.probe_image())))
+    assert T.read_probe(probe) == GOLDEN['swap_perm'].tolist()                 # the permutation, on any Pillow
+    random.seed(T.SWAP_SEED)
+    got = np.array(swap(Image.fromarray(T.swap_image())))
+    want = GOLDEN['swap_image']
+    assert got.shape == want.shape == T.SWAP_IMAGE + (3,) and got.dtype == np.uint8
+    recorded = GOLDEN['swap_pil_version'].tobytes().decode()
+    if PIL.__version__ == recorded:                         # resampling filters may change between Pillow versions
+        assert np.array_equal(got, want)
+    else:
+        print(f'Pillow {PIL.__version__} is not the recorded {recorded}: the bit comparison of the swapped image is left out')
+
+
+def test_collate_functions_match_the_reference(plugin):
+    from hawkeye_amd import data
+    train, val = T.collate_samples()
+    u8 = lambda a: torch.from_numpy(a.astype(np.uint8))
+    ramp = data.dcl_law_ramp(4)
+    got = data.dcl_collate_train([(u8(s[0]), u8(s[1]), s[2], s[3], s[6]) for s in train])
+    assert np.array_equal(got['u8'].numpy(), GOLDEN['collate_train_imgs']) and got['u8'].dtype == torch.uint8
+    assert got['label'].dtype == got['label_swap'].dtype == torch.int64
+    assert np.array_equal(got['label'].numpy(), GOLDEN['collate_train_label']) and np.array_equal(got['label_swap'].numpy(), GOLDEN['collate_train_label_swap'])
+    assert got['label_swap'].tolist() == [1, 0, 1, 0, 7, 207, 5, 205] and got['name'] == [s[6] for s in train]
+    law = GOLDEN['collate_train_law']                       # the laws are the device's work: the ramp at the unswapped rows
+    assert law.dtype == np.float32 and np.array_equal(law[0::2], np.tile(ramp.numpy(), (4, 1)))
+    assert np.array_equal(law[1::2], np.array([T.law_values([int(round(v * 4)) + 2 for v in s[5]], 4) for s in train]))
+    got = data.dcl_collate_val([(u8(s[0]), s[1], s[2], s[5]) for s in val])
+    assert np.array_equal(got['u8'].numpy(), GOLDEN['collate_val_imgs'])
+    assert np.array_equal(got['label'].numpy(), GOLDEN['collate_val_label']) and np.array_equal(got['label_swap'].numpy(), GOLDEN['collate_val_label_swap'])
+    assert np.array_equal(GOLDEN['collate_val_law'], np.tile(ramp.numpy(), (4, 1))) and got['name'] == [s[5] for s in val]
+
+
+def test_datasets_return_the_reference_sample_formats(tmp_path):
+    from PIL import Image
+    from hawkeye_amd import data
+    from hawkeye_amd.transforms import RandomSwap
+    rs = np.random.RandomState(3)
+    lines = []
+    for label in range(3):
+        for n in range(20):
+            Image.fromarray(rs.randint(0, 256, (40, 48, 3), dtype=np.uint8)).save(tmp_path / f'{label}_{n}.png')
+            lines.append(f'{label} {label}_{n}.png')
+    meta = tmp_path / 'meta.txt'
+    meta.write_text('\n'.join(lines) + '\n')
+    tf = {'common_aug': None, 'swap': RandomSwap((3, 3)), 'train_totensor': None, 'val_totensor': None}
+    ds = data.DCLDataset(str(tmp_path), str(meta), tf, (3, 3), 'train', cls_2=True, cls_2xmul=False)
+    un, sw, label, label_swap, name = ds[21]
+    assert len(ds) == 60 and ds.num_classes == 3 and (label, label_swap, name) == (1, -1, '1_1.png')
+    assert un.dtype == sw.dtype == torch.uint8 and tuple(un.shape) == tuple(sw.shape) == (40, 48, 3) and not torch.equal(un, sw)
+    mul = data.DCLDataset(str(tmp_path), str(meta), tf, (3, 3), 'train', cls_2=False, cls_2xmul=True)
+    assert mul[41][2:4] == (2, 5)
+    both = data.DCLDataset(str(tmp_path), str(meta), tf, (3, 3), 'train', cls_2=True, cls_2xmul=True)
+    assert both[41][3] == -1                                # cls_2 is tested last in the reference, so it wins there
+    random.seed(5)
+    val = data.DCLDataset(str(tmp_path), str(meta), tf, (3, 3), 'val')
+    assert len(val) == 6 and sorted(val.labels) == [0, 0, 1, 1, 2, 2]        # a tenth of every class, the reference's default
+    random.seed(5)
+    paths, labels = data.subsample_per_class([l.split()[1] for l in lines], [int(l.split()[0]) for l in lines])
+    assert (paths, labels) == (val.paths, val.labels)
+    img, label, label_swap, name = val[0]
+    assert label == label_swap and tuple(img.shape) == (40, 48, 3)
+    assert len(data.DCLDataset(str(tmp_path), str(meta), tf, (3, 3), 'val', subsample_val=False)) == 60
+    test = data.DCLDataset(str(tmp_path), str(meta), tf, (3, 3), 'test')
+    assert len(test[0]) == 3 and test[0][1:] == (0, '0_0.png')
+    syn = data.SyntheticDCLDataset(5, 21, 4, (7, 7), 'train', seed=2)
+    a, b = syn[3], syn[3]
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and a[2:] == b[2:] and a[3] == -1 and a[0].dtype == torch.uint8
+    tot_u, tot_s = T.patch_totals(a[0].numpy(), (7, 7))[0], T.patch_totals(a[1].numpy(), (7, 7))[0]
+    assert sorted(map(tuple, tot_u.tolist())) == sorted(map(tuple, tot_s.tolist())) and not torch.equal(a[0], a[1])      # whole patches moved
+    assert len(data.SyntheticDCLDataset(5, 21, 4, (7, 7), 'val')[0]) == 4
+
+
+def test_functional_wrappers_refuse_bad_arguments():
+    import hawkeye_amd.functional as F
+    from hawkeye_amd._lib import HawkeyeHipError
+    from hawkeye_amd.model.loss import DCLLoss
+    x, w, bias = torch.randn(2, 3, 4, 4), torch.randn(1, 3, 1, 1), torch.randn(1)
+    logits, swap, mask, law = torch.randn(2, 7), torch.randn(2, 2), torch.rand(2, 4), torch.zeros(2, 4)
+    y = torch.zeros(2, dtype=torch.long)
+    u8 = torch.zeros(1, 14, 14, 3, dtype=torch.uint8)
+    crit = DCLLoss(CfgNode(dict(name='DCLLoss', alpha=1, beta=0.5, gamma=2)))
+    assert (crit.alpha, crit.beta, crit.gamma) == (1, 0.5, 2)
+    for call in (lambda: F.dcl_head(x, w, bias), lambda: F.dcl_loss(logits, swap, mask, y, y, law), lambda: F.dcl_swap_law(u8, u8),
+                 lambda: F.dcl_loss_with_terms(logits, swap, mask, y, y, law, 1, 1, 1), lambda: crit([logits, swap, mask], y, y, law)):
+        with pytest.raises(HawkeyeHipError, match='CPU tensor'):                      # device: no CPU fallback
+            call()
+    bad = [
+        (lambda: F.dcl_head(x[0], w, bias), r'\[B, C, H, W\]'),
+        (lambda: F.dcl_head(x[:, :, :1], w, bias), '2 x 2'),
+        (lambda: F.dcl_head(x, w[:, :2], bias), 'weight must hold 3'),
+        (lambda: F.dcl_head(x, w, torch.zeros(2)), 'bias must hold one'),
+        (lambda: F.dcl_head(x.double(), w.double(), bias.double()), 'fp32'),
+        (lambda: F.dcl_loss(logits, swap[:1], mask, y, y, law), 'one N'),
+        (lambda: F.dcl_loss(logits, swap, mask, y[:1], y, law), 'labels of shape'),
+        (lambda: F.dcl_loss(logits, swap, mask, y, y.float(), law), 'labels_swap must be integers'),
+        (lambda: F.dcl_loss(logits, swap, mask, y, y, law[:, :3]), "mask's shape"),
+        (lambda: F.dcl_loss(logits, swap, mask, y, y, law.long()), 'floating point'),
+        (lambda: F.dcl_swap_law(u8.float(), u8), 'uint8'),
+        (lambda: F.dcl_swap_law(u8, u8[:, :7]), 'one shape'),
+        (lambda: F.dcl_swap_law(u8[:, :3, :3], u8[:, :3, :3]), 'empty'),
+        (lambda: F.dcl_swap_law(u8, u8, (0, 7)), 'positive'),
+    ]
+    for call, message in bad:
+        with pytest.raises(HawkeyeHipError, match=message):
+            call()
+    with pytest.raises(ValueError, match='outputs'):
+        crit([logits, swap], y, y, law)
+
+
+def test_host_side_queries_need_no_gpu():
+    from hawkeye_amd import _lib
+    from hawkeye_amd.transforms import patch_bounds
+    lib = _lib.bind(_lib.load())
+    assert lib.hk_dcl_head_fwd_ws_bytes(16, 2048, 14, 14) >= 16 * 32 * 196 * 4 and lib.hk_dcl_head_bwd_ws_bytes(16, 2048, 14, 14) >= 16 * 2048 * 4
+    assert lib.hk_dcl_head_fwd_ws_bytes(16, 2048, 14, 1) == 0 and lib.hk_dcl_head_bwd_ws_bytes(16, 2048, 1, 14) == 0
+    assert sorted(_lib.PLUGIN_SIGNATURES) == [
+        'hk_dcl_head_bwd', 'hk_dcl_head_bwd_ws_bytes', 'hk_dcl_head_fwd', 'hk_dcl_head_fwd_ws_bytes', 'hk_dcl_loss', 'hk_dcl_swap_law']
+    assert not set(_lib.PLUGIN_SIGNATURES) & set(_lib.SIGNATURES)
+    # the plugin header declares exactly what the table binds, and hawkeye_hip.h pulls it in
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'hawkeye_dcl.h')).read(), flags=re.S)
+    assert sorted(set(re.findall(r'\b(hk_[a-z0-9_]+)\s*\(', src))) == sorted(_lib.PLUGIN_SIGNATURES)
+    assert '#include "hawkeye_dcl.h"' in open(os.path.join(ROOT, 'include', 'hawkeye_hip.h')).read()
+    assert patch_bounds(448, 7) == [0, 64, 128, 192, 256, 320, 384, 448] and patch_bounds(45, 7) == T.patch_bounds(45, 7)
+    assert patch_bounds(45, 7) == [int((45 / 7) * i) for i in range(8)]
+
+
+def test_synthetic_yaml_parses_and_names_the_plugin():
+    cfg = CfgNode.load_cfg(open(os.path.join(ROOT, 'configs', 'DCL_synthetic.yaml')))
+    ref = CfgNode.load_cfg(open(os.path.join(HERE, 'golden', 'reference_configs', 'DCL.yaml')))
+    assert dict(cfg.model) == dict(ref.model) and cfg.train.optimizer == ref.train.optimizer and cfg.train.scheduler == ref.train.scheduler
+    assert cfg.train.criterion == ref.train.criterion and cfg.dataset.batch_size == ref.dataset.batch_size == 8
+    assert cfg.dataset.transformer.image_size == ref.dataset.transformer.image_size and cfg.dataset.transformer.resize_size == 512
+    assert cfg.dataset.name == 'synthetic' and cfg.model.name == 'DCL' and list(cfg.dataset.transformer.swap_num) == [7, 7]
+
+
+def test_trainer_builds_four_parameter_groups_steplr_and_the_transforms(plugin):
+    from PIL import Image
+    ex = importlib.import_module(PLUGIN_MODULES[1])
+    tr = ex.DCLTrainer.__new__(ex.DCLTrainer)
+    net = torch.nn.Module()
+    net.backbone, net.Convmask = torch.nn.Conv2d(3, 4, 3), torch.nn.Conv2d(4, 1, 1)
+    net.classifier, net.classifier_swap = torch.nn.Linear(4, 5, bias=False), torch.nn.Linear(4, 2, bias=False)
+    tr.model = net
+    tr.optimizer = tr.get_optimizer(CfgNode(dict(name='SGD', lr=0.0008, lr_ratio=10, weight_decay=0.00002, momentum=0.9)))
+    tr.scheduler = tr.get_scheduler(CfgNode(dict(name='StepLR', step_size=60, gamma=0.1)))
+    groups = tr.optimizer.param_groups
+    assert isinstance(tr.optimizer, torch.optim.SGD) and tr.optimizer.defaults['momentum'] == 0.9 and tr.optimizer.defaults['weight_decay'] == 0
+    assert [g['lr'] for g in groups] == pytest.approx([0.0008, 0.008, 0.008, 0.008])
+    assert [[id(q) for q in g['params']] for g in groups] == [[id(q) for q in m.parameters()] for m in (net.backbone, net.classifier, net.classifier_swap, net.Convmask)]
+    assert isinstance(tr.scheduler, torch.optim.lr_scheduler.StepLR)
+    assert isinstance(tr.get_criterion(CfgNode(dict(name='DCLLoss', alpha=1, beta=1, gamma=1))), ex.DCLLoss)
+    lrs = []
+    for _ in range(62):
+        lrs.append([g['lr'] for g in groups])
+        tr.optimizer.step()
+        tr.scheduler.step()
+    assert lrs[59] == pytest.approx([0.0008, 0.008, 0.008, 0.008]) and lrs[60] == pytest.approx([0.00008, 0.0008, 0.0008, 0.0008])
+    tf = tr.get_transformers(CfgNode(dict(image_size=56, resize_size=64)))
+    img = Image.fromarray(np.random.RandomState(0).randint(0, 256, (50, 80, 3), dtype=np.uint8))
+    aug = tf['common_aug'](img)
+    assert aug.size == (56, 56) and tf['swap'](aug).size == (56, 56) and tf['train_totensor'](aug).size == (56, 56) and tf['swap_num'] == [7, 7]
+    assert tr.get_collate_fn()['train'] is ex.data.dcl_collate_train and tr.get_collate_fn()['val'] is ex.data.dcl_collate_val
+    tr.config, tr.num_classes = CfgNode(dict(model=dict(cls_2xmul=True))), 3
+    a, b = torch.randn(2, 3), torch.randn(2, 6)
+    assert torch.equal(tr.class_logits([a, b, None]), a + b[:, :3] + b[:, 3:])
+    tr.config = CfgNode(dict(model=dict(cls_2xmul=False)))
+    assert tr.class_logits([a, b, None]) is a
+
+
+def test_golden_inputs_are_a_pure_function_of_the_recipe_and_the_files_are_small():
+    a, b = T.loss_inputs(1), T.loss_inputs(1)
+    assert all(np.array_equal(u, v) for u, v in zip(a[:6], b[:6])) and a[2].shape == (4, 49) and a[2].dtype == np.float32 and a[3].dtype == np.int64
+    largest = max(os.path.getsize(os.path.join(HERE, 'golden', f)) for f in os.listdir(os.path.join(HERE, 'golden'))
+                  if f.endswith('.npz') and not f.startswith('dcl_'))
+    for f in T.FILES + ('dcl_state_dict.json',):
+        assert os.path.getsize(os.path.join(HERE, 'golden', f)) <= largest
+    for case in T.load_loss_cases():
+        assert case['loss_f64'].dtype == np.float64 and case['loss_f32'].dtype == np.float32 and case['loss_f64'].shape == (4,)
+        assert case['d_mask_f64'].shape == (case['N'], case['M'])
+        t = case['loss_f64']
+        assert abs(t[0] - (T.COEF[0] * t[1] + T.COEF[1] * t[2] + T.COEF[2] * t[3])) < 1e-12
+        gap = np.abs(case['mask'].astype(np.float64) - case['law'])
+        if case['k'] == T.TIE_CASE:
+            assert all(gap[b, e] == 0 for b, e in T.TIES) and np.sort(gap.ravel())[len(T.TIES)] >= T.L1_MARGIN
+            assert all(case['d_mask_f64'][b, e] == 0 for b, e in T.TIES)
+        else:
+            assert gap.min() >= T.L1_MARGIN                 # the accepted seed keeps the L1 term away from its kink
+    img, swapped, perm = T.law_permutation_case()
+    assert len(set(T.patch_totals(img, (7, 7))[0].sum(1).tolist())) == 49 and sorted(perm.tolist()) == list(range(49))
+    assert np.array_equal(GOLDEN['law_permutation_index'], perm) and GOLDEN['law_large_index'].shape == (49,)
+    model = T.load_model_case()
+    assert model['logits_f64'].shape == (2, 200) and model['swap_logits_f32'].shape == (2, 2) and model['mask_f64'].shape == (2, 49)
+
+
+@pytest.fixture
+def emulated_kernels():
+    from emu import build_emu
+    from emu.harness import emulated
+    if build_emu._compiler() is None:
+        pytest.skip('no clang++ to build the emulated kernels')
+    with emulated():
+        yield
+
+
+@pytest.mark.parametrize('k', [0, 1])
+def test_loss_module_on_the_emulated_library_matches_the_golden(emulated_kernels, k):
+    from hawkeye_amd.model.loss import DCLLoss
+    case = T.load_loss_cases()[k]
+    leaves = [torch.from_numpy(case[n]).requires_grad_(True) for n in ('logits', 'swap', 'mask')]
+    crit = DCLLoss(CfgNode(dict(alpha=T.COEF[0], beta=T.COEF[1], gamma=T.COEF[2])))
+    loss = crit(leaves, torch.from_numpy(case['y']), torch.from_numpy(case['ys']), torch.from_numpy(case['law']))
+    loss.backward()
+    T.judge_value('DCLLoss', 'total', loss.item(), case['loss_f32'][0], case['loss_f64'][0])
+    for name, t in zip(T.LOSS_RESULTS[1:], leaves):
+        T.judge_value('DCLLoss', name, t.grad.numpy(), case[f'{name}_f32'], case[f'{name}_f64'])
+
+
+def test_whole_model_forward_on_the_emulated_library_matches_the_golden(plugin, emulated_kernels):
+    """The trunk on torch's CPU kernels, the head and both classifiers on the emulated library."""
+    from inputs import seeded_init
+    case = T.load_model_case()
+    net = plugin.DCL(config(case['cls_2'], case['cls_2xmul']))
+    seeded_init(net, case['init_seed'])
+    net.eval()
+    with torch.no_grad():
+        out = net(torch.from_numpy(case['images']))
+    assert isinstance(out, list) and len(out) == 3
+    for name, t in zip(T.MODEL_OUTPUTS, out):
+        T.judge_value('whole model (emulated head)', name, t.numpy(), case[f'{name}_f32'], case[f'{name}_f64'])
+    assert out[0].argmax(1).tolist() == case['logits_f64'].argmax(1).tolist()
+
+
+def reference_dir():
+    d = os.environ.get('HAWKEYE_REFERENCE', os.path.join(os.path.dirname(ROOT), 'reference'))
+    return d if os.path.isfile(os.path.join(d, 'model', 'methods', 'DCL.py')) else None
+
+
+@pytest.mark.skipif(reference_dir() is None, reason='the reference checkout is not present')
+def test_golden_tool_check_reproduces_the_committed_bytes():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_dcl_golden.py'), '--check', '--reference', reference_dir()],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    print(r.stdout[-3000:], r.stderr[-2000:])
+    assert r.returncode == 0 and r.stdout.count('identical') == len(T.FILES) + 1 and 'DIFFERENT' not in r.stdout
