@@ -19,7 +19,7 @@ c_sz = ctypes.c_size_t
 c_ll = ctypes.c_longlong
 c_fl = ctypes.c_float
 
-# name -> (restype, argtypes); mirrors include/hawkeye_hip.h one to one (include/hawkeye_dcl.h: PLUGIN_SIGNATURES below)
+# name -> (restype, argtypes); mirrors include/hawkeye_hip.h one to one
 SIGNATURES = {
     'hk_version': (ctypes.c_char_p, []),
     'hk_tuning_set': (c_i, [ctypes.c_char_p, c_i]),
@@ -120,10 +120,6 @@ SIGNATURES = {
     'hk_image_finalize': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     'hk_bgemm_f32': (c_i, [c_f, c_i, c_ll, c_i, c_f, c_i, c_ll, c_i, c_f, c_i, c_ll, c_i, c_i, c_i, c_i,
                            c_fl, c_fl, c_fl, c_f]),
-}
-
-# the entry points of include/hawkeye_dcl.h (plugins added after the table above was closed; same conventions)
-PLUGIN_SIGNATURES = {
     'hk_dcl_head_fwd_ws_bytes': (c_sz, [c_i] * 4),
     'hk_dcl_head_fwd': (c_i, [c_f] * 5 + [c_i] * 4 + [c_f, c_sz, c_f]),
     'hk_dcl_head_bwd_ws_bytes': (c_sz, [c_i] * 4),
@@ -133,15 +129,13 @@ PLUGIN_SIGNATURES = {
 }
 
 
-def bind(lib):
-    """Attach the prototypes of PLUGIN_SIGNATURES to a loaded library (the gfx950 build, or whatever stands in for it);
-    done once per library object.  Returns the library."""
-    if not getattr(lib, '_hk_plugins_bound', False):
-        for name, (res, args) in PLUGIN_SIGNATURES.items():
-            fn = getattr(lib, name)   # AttributeError => header/library drifted apart
-            fn.restype = res
-            fn.argtypes = args
-        lib._hk_plugins_bound = True
+def attach(lib):
+    """Give every function of SIGNATURES its prototype on a library object (the gfx950 build, or whatever stands in for
+    it).  Returns the library."""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)   # AttributeError => header/library drifted apart
+        fn.restype = res
+        fn.argtypes = args
     return lib
 
 
@@ -164,13 +158,8 @@ def load():
         raise HawkeyeHipError(
             f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
             f'or `make -C hawkeye_amd/csrc` (there is no CPU fallback for the HIP ops)')
-    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)   # AttributeError => header/library drifted apart
-        fn.restype = res
-        fn.argtypes = args
-    _lib = bind(lib)
-    return lib
+    _lib = attach(ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL))
+    return _lib
 
 
 def check(rc, what):

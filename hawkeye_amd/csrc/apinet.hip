@@ -24,21 +24,13 @@
 #include <cmath>
 
 #include "hk_common.h"
-#include "hk_ce_row.h"
+#include "hk_rows.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
 
 constexpr int API_THREADS = 256;
 constexpr int API_WAVES = API_THREADS / WAVE;
-
-template <bool ALIGNED>
-__device__ __forceinline__ f32x4 api_load4(const float* p) {
-    if (ALIGNED) return *reinterpret_cast<const f32x4*>(p);
-    f32x4 v;
-    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-    return v;
-}
 
 // One wave: sum_d (a[d] - b[d])^2.  The order depends on D alone (QUAD: D % 4 == 0, lane l owns the quads l, l + 64, ..;
 // otherwise the elements l, l + 64, ..); alignment only decides how a quad is fetched.
@@ -48,7 +40,7 @@ __device__ __forceinline__ float api_sqdist(const float* a, const float* b, int 
     float s = 0.f;
     if (QUAD) {
         for (int q = lane; q < (D >> 2); q += WAVE) {
-            const f32x4 va = api_load4<ALIGNED>(a + 4 * q), vb = api_load4<ALIGNED>(b + 4 * q);
+            const f32x4 va = load4a<ALIGNED>(a + 4 * q), vb = load4a<ALIGNED>(b + 4 * q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float d = va[e] - vb[e];
@@ -220,12 +212,12 @@ __global__ __launch_bounds__(API_THREADS) void apinet_loss_rows_kernel(const flo
     const int y = labels[r];
     const float* rs = ls_ + (size_t)r * C;
     const float* ro = lo_ + (size_t)r * C;
-    const ApiRow s = api_row_stats(rs, C, y, smoothing), o = api_row_stats(ro, C, y, smoothing);
+    const CeRow s = ce_row_stats(rs, C, y, smoothing), o = ce_row_stats(ro, C, y, smoothing);
     const float hinge = (o.py - s.py) + margin;                        // MarginRankingLoss(self, other, +1)
     const bool active = hinge > 0.f;                                   // NaN: inactive here, the loss is NaN through ce
     const float w_ce = 0.5f / (float)R, w_rank = active ? 1.f / (float)R : 0.f;
-    api_row_grad(rs, dself + (size_t)r * C, C, y, smoothing, s, w_ce, -w_rank);
-    api_row_grad(ro, dother + (size_t)r * C, C, y, smoothing, o, w_ce, w_rank);
+    ce_row_grad(rs, dself + (size_t)r * C, C, y, smoothing, s, w_ce, -w_rank);
+    ce_row_grad(ro, dother + (size_t)r * C, C, y, smoothing, o, w_ce, w_rank);
     if ((threadIdx.x & 63) == 0) {
         ce_rows[r] = s.ce + o.ce;
         rank_rows[r] = active ? hinge : (hinge != hinge ? hinge : 0.f);

@@ -22,7 +22,7 @@
 #include <cmath>
 
 #include "hk_common.h"
-#include "hk_ce_row.h"
+#include "hk_rows.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -30,28 +30,6 @@ namespace hk {
 constexpr int CX_MAX_P = 3;
 constexpr int ME_THREADS = 256;
 constexpr int ME_WAVES = ME_THREADS / WAVE;
-constexpr int ME_STEP = WAVE * 4;                      // elements of a row that one wave covers per trip
-
-// elements i .. i + 3 of a row of n floats; past the end: 0
-template <bool VEC>
-__device__ __forceinline__ f32x4 cx_load4(const float* row, int i, int n) {
-    if (VEC) return *reinterpret_cast<const f32x4*>(row + i);
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = i + e < n ? row[i + e] : 0.f;
-    return v;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void cx_store4(float* row, int i, int n, f32x4 v) {
-    if (VEC) {
-        *reinterpret_cast<f32x4*>(row + i) = v;
-        return;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (i + e < n) row[i + e] = v[e];
-}
 
 __device__ __forceinline__ float cx_relu(float v) { return v > 0.f ? v : (v == v ? 0.f : v); }      // a NaN stays one, as torch's relu keeps it
 
@@ -73,18 +51,18 @@ __global__ __launch_bounds__(ME_THREADS) void crossx_me_fwd_kernel(const float* 
         acc[p] = MODE == 0 ? -INFINITY : 0.f;
         idx[p] = 0x7fffffff;
     }
-    for (int i = lane * 4; i < HW; i += ME_STEP) {
-        const f32x4 o = cx_load4<VEC>(out + base, i, HW), r = cx_load4<VEC>(res + base, i, HW);
+    for (int i = lane * 4; i < HW; i += ROW_STEP) {
+        const f32x4 o = load4<VEC>(out + base, i, HW), r = load4<VEC>(res + base, i, HW);
         f32x4 m;
 #pragma unroll
         for (int e = 0; e < 4; ++e) m[e] = cx_relu(o[e] + r[e]);
-        cx_store4<VEC>(mainmap + base, i, HW, m);
+        store4<VEC>(mainmap + base, i, HW, m);
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = cx_relu(o[e] * g[p] + r[e]);
-            cx_store4<VEC>(parts + p * pstride + base, i, HW, v);
+            store4<VEC>(parts + p * pstride + base, i, HW, v);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (!VEC && i + e >= HW) continue;
@@ -145,16 +123,16 @@ __global__ __launch_bounds__(ME_THREADS) void crossx_me_bwd_kernel(const float* 
     }
     const float zadd = dz ? dz[row] / (float)HW : 0.f;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (int i = lane * 4; i < HW; i += ME_STEP) {
-        const f32x4 o = cx_load4<VEC>(out + base, i, HW), m = cx_load4<VEC>(mainmap + base, i, HW);
-        const f32x4 dm = d_main ? cx_load4<VEC>(d_main + base, i, HW) : zero;
+    for (int i = lane * 4; i < HW; i += ROW_STEP) {
+        const f32x4 o = load4<VEC>(out + base, i, HW), m = load4<VEC>(mainmap + base, i, HW);
+        const f32x4 dm = d_main ? load4<VEC>(d_main + base, i, HW) : zero;
         f32x4 dout, dres;
 #pragma unroll
         for (int e = 0; e < 4; ++e) dout[e] = dres[e] = m[e] > 0.f ? dm[e] : 0.f;
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            const f32x4 v = cx_load4<VEC>(parts + p * pstride + base, i, HW);
-            const f32x4 dv = d_parts ? cx_load4<VEC>(d_parts + p * pstride + base, i, HW) : zero;
+            const f32x4 v = load4<VEC>(parts + p * pstride + base, i, HW);
+            const f32x4 dv = d_parts ? load4<VEC>(d_parts + p * pstride + base, i, HW) : zero;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float pool = MODE == 1 ? dp[p] : (i + e == am[p] ? dp[p] : 0.f);
@@ -166,8 +144,8 @@ __global__ __launch_bounds__(ME_THREADS) void crossx_me_bwd_kernel(const float* 
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) dout[e] += zadd;
-        cx_store4<VEC>(d_out + base, i, HW, dout);
-        cx_store4<VEC>(d_res + base, i, HW, dres);
+        store4<VEC>(d_out + base, i, HW, dout);
+        store4<VEC>(d_res + base, i, HW, dres);
     }
 #pragma unroll
     for (int p = 0; p < P; ++p) {
@@ -239,12 +217,6 @@ struct CxLossArgs {
     float* g;                      // [P, C_0 + C_1 + C_2]: list l at column offset C_0 + .. + C_(l-1)
 };
 
-__device__ __forceinline__ float cx_wave_total(const float* v, int n) {
-    float s = 0.f;
-    for (int r = threadIdx.x & 63; r < n; r += WAVE) s += v[r];
-    return wave_sum(s);
-}
-
 __global__ __launch_bounds__(CX_LOSS_THREADS) void crossx_loss_kernel(const CxLossArgs A) {
 #pragma clang fp contract(off)
     __shared__ float red[CX_LOSS_WAVES];
@@ -262,8 +234,8 @@ __global__ __launch_bounds__(CX_LOSS_THREADS) void crossx_loss_kernel(const CxLo
         for (int k = lane; k < K; k += WAVE) sum[k] = (u[k] + p[k]) + c[k];            // read back by the lane that wrote it
         const long long yl = A.labels[b];
         const int y = (yl >= 0 && yl < K) ? (int)yl : -1;
-        const ApiRow ss = api_row_stats(sum, K, y, smoothing);
-        const ApiRow su = api_row_stats(u, K, -1, 0.f), sp = api_row_stats(p, K, -1, 0.f), sc = api_row_stats(c, K, -1, 0.f);
+        const CeRow ss = ce_row_stats(sum, K, y, smoothing);
+        const CeRow su = ce_row_stats(u, K, -1, 0.f), sp = ce_row_stats(p, K, -1, 0.f), sc = ce_row_stats(c, K, -1, 0.f);
         // t_k = 2 log pu_k - log pp_k - log pc_k ; kl_row = sum_k pu_k t_k = KL(pu | pp) + KL(pu | pc)
         float kl = 0.f;
         for (int k = lane; k < K; k += WAVE) {
@@ -355,7 +327,7 @@ __global__ __launch_bounds__(CX_LOSS_THREADS) void crossx_loss_kernel(const CxLo
         for (int k = lane; k < C; k += WAVE) dx[k] = A.weight * ((g[k] - (x[k] * inv) * d) * inv);
     }
     if (wave == 0) {
-        const float ce = cx_wave_total(A.ce_rows, B), kl = cx_wave_total(A.kl_rows, B);
+        const float ce = wave_total(A.ce_rows, B), kl = wave_total(A.kl_rows, B);
         if (lane == 0) {
             const float cls = ce / (float)B, klm = kl / (float)B;
             A.loss[0] = (((reg[0] + reg[1]) + reg[2]) + klm) + cls;                    // the reference's order of addition
@@ -399,7 +371,7 @@ static bool me_sizes_ok(int P, int N, int C, int HW, long long& rows, unsigned& 
     rows = (long long)N * C;
     const long long nb = (rows + ME_WAVES - 1) / ME_WAVES;
     blocks = (unsigned)nb;
-    return nb <= 0x7fffffff && HW <= 0x7fffffff - ME_STEP && P * rows <= 0x7fffffffLL;
+    return nb <= 0x7fffffff && HW <= 0x7fffffff - ROW_STEP && P * rows <= 0x7fffffffLL;
 }
 
 }  // namespace hk

@@ -15,7 +15,7 @@
 //          d_mask and the saved mask, x is read once (for dw), dx written once; dw leaves as one partial per (sample,
 //          channel) that a second launch adds sample by sample, together with dbias.  No atomics.
 //          The products are not contracted into fmas: w[c] * x is rounded, then added, as the reference's two ops are.
-//   loss   one workgroup of 16 waves, a wave per sample: both cross entropies (hk_ce_row.h), the row's share of the L1 term
+//   loss   one workgroup of 16 waves, a wave per sample: both cross entropies (hk_rows.h), the row's share of the L1 term
 //          and the three gradients; the waves' totals meet in LDS in wave order.  One launch, no workspace.
 //   law    one workgroup per image.  A wave per patch: exact integer band totals of the unswapped and the swapped patch,
 //          then in float64 ((0 + s_r / n) + s_g / n) + s_b / n - Python's sum() of ImageStat's means.  A thread per swapped
@@ -23,7 +23,7 @@
 #include <cmath>
 
 #include "hk_common.h"
-#include "hk_ce_row.h"
+#include "hk_rows.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -32,35 +32,13 @@ constexpr int DH_THREADS = 256;
 constexpr int DH_WAVES = DH_THREADS / WAVE;
 constexpr int DH_CPW = 16;                             // rows (channels of one sample) that a wave owns
 constexpr int DH_CHUNK = DH_WAVES * DH_CPW;            // channels per workgroup
-constexpr int DH_STEP = WAVE * 4;                      // elements of a row that one wave covers per trip
-
-// elements i .. i + 3 of a row of n floats; past the end: 0
-template <bool VEC>
-__device__ __forceinline__ f32x4 dcl_load4(const float* row, int i, int n) {
-    if (VEC) return *reinterpret_cast<const f32x4*>(row + i);
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = i + e < n ? row[i + e] : 0.f;
-    return v;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void dcl_store4(float* row, int i, int n, f32x4 v) {
-    if (VEC) {
-        *reinterpret_cast<f32x4*>(row + i) = v;
-        return;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (i + e < n) row[i + e] = v[e];
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(DH_THREADS) void dcl_head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                   float* __restrict__ pooled, float* __restrict__ part, int C, int HW,
                                                                   int nchunk) {
 #pragma clang fp contract(off)
-    __shared__ float red[DH_WAVES][DH_STEP];
+    __shared__ float red[DH_WAVES][ROW_STEP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.x / nchunk, chunk = blockIdx.x - b * nchunk;
     const int c0 = chunk * DH_CHUNK + wave * DH_CPW;
@@ -74,14 +52,14 @@ __global__ __launch_bounds__(DH_THREADS) void dcl_head_fwd_kernel(const float* _
     }
     const float* xb = x + ((size_t)b * C + (nc ? c0 : 0)) * HW;
     float* pb = part + (size_t)blockIdx.x * HW;
-    for (int t0 = 0; t0 < HW; t0 += DH_STEP) {                                      // every thread makes every trip: barriers below
+    for (int t0 = 0; t0 < HW; t0 += ROW_STEP) {                                      // every thread makes every trip: barriers below
         const int i = t0 + lane * 4;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         if (i < HW) {
 #pragma unroll
             for (int k = 0; k < DH_CPW; ++k) {
                 if (k < nc) {
-                    const f32x4 v = dcl_load4<VEC>(xb + (size_t)k * HW, i, HW);
+                    const f32x4 v = load4<VEC>(xb + (size_t)k * HW, i, HW);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         acc[e] += wc[k] * v[e];
@@ -153,7 +131,7 @@ __global__ __launch_bounds__(DH_THREADS) void dcl_head_bwd_kernel(const float* _
     const size_t base = ((size_t)b * C + c0) * HW;
     const float* mk = mask + (size_t)b * Mh * Mw;
     const float* dm = d_mask ? d_mask + (size_t)b * Mh * Mw : nullptr;
-    for (int i = lane * 4; i < HW; i += DH_STEP) {
+    for (int i = lane * 4; i < HW; i += ROW_STEP) {
         f32x4 gq = {0.f, 0.f, 0.f, 0.f};                                            // g / 4 at the element's window; 0 outside the pooled area
         if (dm) {
 #pragma unroll
@@ -172,7 +150,7 @@ __global__ __launch_bounds__(DH_THREADS) void dcl_head_bwd_kernel(const float* _
         for (int k = 0; k < DH_CPW; ++k) {
             if (k < nc) {
                 if (dwpart) {
-                    const f32x4 v = dcl_load4<VEC>(x + base + (size_t)k * HW, i, HW);
+                    const f32x4 v = load4<VEC>(x + base + (size_t)k * HW, i, HW);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) da[k] += v[e] * gq[e];
                 }
@@ -180,7 +158,7 @@ __global__ __launch_bounds__(DH_THREADS) void dcl_head_bwd_kernel(const float* _
                     f32x4 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = dp[k] + wc[k] * gq[e];
-                    dcl_store4<VEC>(dx + base + (size_t)k * HW, i, HW, o);
+                    store4<VEC>(dx + base + (size_t)k * HW, i, HW, o);
                 }
             }
         }
@@ -255,12 +233,12 @@ __global__ __launch_bounds__(DL_THREADS) void dcl_loss_kernel(const DclLossArgs 
         const long long yl = A.labels[b], zl = A.labels_swap[b];
         const int y = (yl >= 0 && yl < K) ? (int)yl : -1, z = (zl >= 0 && zl < S) ? (int)zl : -1;
         const float* row = A.logits + (size_t)b * K;
-        const ApiRow r = api_row_stats(row, K, y, A.smoothing);
-        api_row_grad(row, A.d_logits + (size_t)b * K, K, y, A.smoothing, r, w_ce, 0.f);
+        const CeRow r = ce_row_stats(row, K, y, A.smoothing);
+        ce_row_grad(row, A.d_logits + (size_t)b * K, K, y, A.smoothing, r, w_ce, 0.f);
         ce += r.ce;
         const float* srow = A.swap + (size_t)b * S;
-        const ApiRow q = api_row_stats(srow, S, z, A.smoothing);
-        api_row_grad(srow, A.d_swap + (size_t)b * S, S, z, A.smoothing, q, w_sw, 0.f);
+        const CeRow q = ce_row_stats(srow, S, z, A.smoothing);
+        ce_row_grad(srow, A.d_swap + (size_t)b * S, S, z, A.smoothing, q, w_sw, 0.f);
         sw += q.ce;
         float s = 0.f;
         for (int m = lane; m < M; m += WAVE) {
@@ -356,7 +334,7 @@ static int head_sizes(int B, int C, int H, int W, int& nchunk) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return HK_ERR_BAD_ARG;
     nchunk = (C + DH_CHUNK - 1) / DH_CHUNK;
     if (H < 2 || W < 2) return HK_ERR_UNSUPPORTED;     // AvgPool2d(2) has no output there
-    if ((long long)H * W > 0x7fffffffLL - DH_STEP || (long long)B * nchunk > 0x7fffffffLL || (long long)B * C > 0x7fffffffLL ||
+    if ((long long)H * W > 0x7fffffffLL - ROW_STEP || (long long)B * nchunk > 0x7fffffffLL || (long long)B * C > 0x7fffffffLL ||
         (long long)B * (H / 2) * (W / 2) > 0x7fffffffLL)
         return HK_ERR_UNSUPPORTED;
     return HK_OK;

@@ -21,7 +21,7 @@
 #include <cmath>
 
 #include "hk_common.h"
-#include "hk_ce_row.h"
+#include "hk_rows.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -182,13 +182,6 @@ constexpr int NTS_LOSS_THREADS = 1024;
 constexpr int NTS_LOSS_WAVES = NTS_LOSS_THREADS / WAVE;
 constexpr long long NTS_MAX_ROWS = 1 << 22;            // B (N + 2): one workgroup walks the rows; far above any batch
 
-// sum of v[0 .. n) by one wave: lane l adds l, l + 64, .. then the butterfly - a fixed order
-__device__ __forceinline__ float nts_wave_total(const float* v, int n) {
-    float s = 0.f;
-    for (int r = threadIdx.x & 63; r < n; r += WAVE) s += v[r];
-    return wave_sum(s);
-}
-
 __global__ __launch_bounds__(NTS_LOSS_THREADS) void nts_loss_kernel(const float* __restrict__ raw, const float* __restrict__ concat,
                                                                     const float* __restrict__ part, const float* __restrict__ prob,
                                                                     const int32_t* __restrict__ labels, float smoothing,
@@ -215,8 +208,8 @@ __global__ __launch_bounds__(NTS_LOSS_THREADS) void nts_loss_kernel(const float*
             w = 1.f / (float)P;
         }
         const int y = labels[b];
-        const ApiRow s = api_row_stats(row, C, y, smoothing);
-        api_row_grad(row, out, C, y, smoothing, s, w, 0.f);
+        const CeRow s = ce_row_stats(row, C, y, smoothing);
+        ce_row_grad(row, out, C, y, smoothing, s, w, 0.f);
         if (lane == 0) {
             ce_rows[r] = s.ce;
             if (r >= 2 * B) part_loss[r - 2 * B] = (y >= 0 && y < C) ? s.ls - (row[y] - s.mx) : NAN;     // no smoothing
@@ -243,8 +236,8 @@ __global__ __launch_bounds__(NTS_LOSS_THREADS) void nts_loss_kernel(const float*
     }
     __syncthreads();
     if (wave == 0) {
-        const float a = nts_wave_total(ce_rows, B), c = nts_wave_total(ce_rows + B, B);
-        const float p = nts_wave_total(ce_rows + 2 * B, P), k = nts_wave_total(rank_rows, P);
+        const float a = wave_total(ce_rows, B), c = wave_total(ce_rows + B, B);
+        const float p = wave_total(ce_rows + 2 * B, P), k = wave_total(rank_rows, P);
         if (lane == 0) {
             const float l_raw = a / (float)B, l_cat = c / (float)B, l_part = p / (float)P, l_rank = k / (float)B;
             loss[0] = ((l_raw + l_rank) + l_cat) + l_part;                 // the reference's order of addition

@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "hk_common.h"
+#include "hk_rows.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -28,23 +29,6 @@ constexpr int PEER_WAVES = PEER_THREADS / WAVE;
 constexpr int PEER_ROW_WAVES = 4;                     // rows / grad kernels: 4 (row, net) items per 256-thread workgroup
 constexpr int PEER_MAX_N = 2048;                      // select keeps 6 N + 32 words in LDS (48 KB at the bound)
 constexpr size_t PEER_LDS_LIMIT = 160 * 1024;         // what one workgroup may hold on gfx950 (no static LDS in these kernels)
-
-// the four floats at quad q of a row; ALIGNED: one 16-byte access
-template <bool ALIGNED>
-__device__ __forceinline__ f32x4 peer_load4(const float* p) {
-    if (ALIGNED) return *reinterpret_cast<const f32x4*>(p);
-    f32x4 v;
-    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-    return v;
-}
-template <bool ALIGNED>
-__device__ __forceinline__ void peer_store4(float* p, f32x4 v) {
-    if (ALIGNED) {
-        *reinterpret_cast<f32x4*>(p) = v;
-    } else {
-        p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
-    }
-}
 
 struct RowStat {
     int pred;
@@ -59,7 +43,7 @@ __device__ __forceinline__ RowStat peer_row_stats(const float* row, int C, int y
     int idx = 0x7fffffff;
     if (QUAD) {
         for (int q = lane; q < (C >> 2); q += WAVE) {
-            const f32x4 v = peer_load4<ALIGNED>(row + 4 * q);
+            const f32x4 v = load4a<ALIGNED>(row + 4 * q);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (v[e] > m) { m = v[e]; idx = 4 * q + e; }
@@ -79,7 +63,7 @@ __device__ __forceinline__ RowStat peer_row_stats(const float* row, int C, int y
     float s = 0.f;
     if (QUAD) {
         for (int q = lane; q < (C >> 2); q += WAVE) {
-            const f32x4 v = peer_load4<ALIGNED>(row + 4 * q);
+            const f32x4 v = load4a<ALIGNED>(row + 4 * q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) s += expf(v[e] - m);
         }
@@ -104,11 +88,11 @@ __device__ __forceinline__ void peer_row_grad(const float* row, float* out, int 
         for (int q = lane; q < (C >> 2); q += WAVE) {
             f32x4 g = {0.f, 0.f, 0.f, 0.f};
             if (live) {
-                const f32x4 v = peer_load4<ALIGNED_IN>(row + 4 * q);
+                const f32x4 v = load4a<ALIGNED_IN>(row + 4 * q);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) g[e] = w * (expf((v[e] - mx) - ls) - (4 * q + e == y ? 1.f : 0.f));
             }
-            peer_store4<ALIGNED_OUT>(out + 4 * q, g);
+            store4a<ALIGNED_OUT>(out + 4 * q, g);
         }
     } else {
         for (int c = lane; c < C; c += WAVE)

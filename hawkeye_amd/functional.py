@@ -19,6 +19,44 @@ def _f32c(t):
     return t.contiguous()
 
 
+def _f32_shaped(t, shape, what, name):
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.HawkeyeHipError(f'{what}: {name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    return _f32c(t)
+
+
+def _int_tensor(t, shape, dtype, device, what, name, same_device=False):
+    """An integer argument (labels, indices, boxes) of the given shape -> contiguous `dtype` on `device`, converted there
+    (no host round trip).  same_device: a tensor that lives elsewhere is refused instead of moved."""
+    if t.is_floating_point() or t.dtype == torch.bool:
+        raise _lib.HawkeyeHipError(f'{what}: {name} must be integers; got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.HawkeyeHipError(f'{what}: {name} must have the shape {tuple(shape)}, got {name} of shape {tuple(t.shape)}')
+    if same_device and t.device != device:
+        raise _lib.HawkeyeHipError(f'{what}: {name} on {t.device} but the data on {device}')
+    return t.to(device=device, dtype=dtype).contiguous()
+
+
+def _one_device(what, device, *tensors):
+    for t in tensors:
+        if t.device != device:
+            raise _lib.HawkeyeHipError(f'{what}: tensors on {device} and {t.device}')
+
+
+def _loss_forward(ctx, loss, grads):
+    """The end of a fused loss's forward.  loss = [total, terms ..]; grads: the gradients of the total, which backward only
+    scales -> (total, terms), the terms not differentiable."""
+    ctx.save_for_backward(*grads)
+    terms = loss[1:]
+    ctx.mark_non_differentiable(terms)
+    return loss[0], terms
+
+
+def _loss_backward(ctx, g, rest):
+    """Every saved gradient times the incoming one, then a None for each of the `rest` inputs that take none."""
+    return tuple(t * g for t in ctx.saved_tensors) + (None,) * rest
+
+
 def _on(device):
     """Make `device` the current HIP device for a host-side ABI call (memcpy + stream of that device)."""
     return torch.cuda.device(device)
@@ -788,9 +826,7 @@ class _NPairsLoss(torch.autograd.Function):
         lib = _lib.load()
         parts = _f32c(parts)
         b, p, d = parts.shape
-        labels = targets.to(device=parts.device, dtype=torch.int32).contiguous()
-        if labels.shape != (b,):
-            raise _lib.HawkeyeHipError(f'npairs_loss: {b} samples but targets of shape {tuple(targets.shape)}')
+        labels = _int_tensor(targets, (b,), torch.int32, parts.device, 'npairs_loss', 'targets')
         loss = torch.empty(1, dtype=torch.float32, device=parts.device)
         dx = torch.empty_like(parts)
         nws = lib.hk_npairs_ws_bytes(b * p, d)
@@ -802,8 +838,7 @@ class _NPairsLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        (dx,) = ctx.saved_tensors
-        return dx * g, None
+        return _loss_backward(ctx, g, 1)
 
 
 def npairs_loss(parts, targets):
@@ -816,15 +851,9 @@ def _peer_args(logits_1, logits_2, labels, drop_rate):
     if logits_1.dim() != 2 or logits_1.shape != logits_2.shape:
         raise _lib.HawkeyeHipError(f'peer_learning_loss: logits of shapes {tuple(logits_1.shape)} and {tuple(logits_2.shape)}; '
                                    f'two [N, C] matrices of one shape are needed')
-    if logits_1.device != logits_2.device:
-        raise _lib.HawkeyeHipError(f'peer_learning_loss: logits on {logits_1.device} and {logits_2.device}')
+    _one_device('peer_learning_loss', logits_1.device, logits_2)
     l1, l2 = _f32c(logits_1), _f32c(logits_2)          # dense copies of views; the kernels read rows of C floats
-    n = l1.shape[0]
-    if labels.is_floating_point() or labels.dtype == torch.bool:
-        raise _lib.HawkeyeHipError(f'peer_learning_loss: labels must be integers; got {labels.dtype}')
-    if tuple(labels.shape) != (n,):
-        raise _lib.HawkeyeHipError(f'peer_learning_loss: {n} rows but labels of shape {tuple(labels.shape)}')
-    y = labels.to(device=l1.device, dtype=torch.int32).contiguous()       # converted on the device, no host round trip
+    y = _int_tensor(labels, (l1.shape[0],), torch.int32, l1.device, 'peer_learning_loss', 'labels')
     return l1, l2, y, float(drop_rate)
 
 
@@ -888,14 +917,7 @@ def _api_pool(pool, what):
 
 
 def _api_partner(partner, pool, what):
-    b = pool.shape[0]
-    if partner.is_floating_point() or partner.dtype == torch.bool:
-        raise _lib.HawkeyeHipError(f'{what}: partner must be integers; got {partner.dtype}')
-    if tuple(partner.shape) != (2 * b,):
-        raise _lib.HawkeyeHipError(f'{what}: {b} rows need a partner of shape ({2 * b},), got {tuple(partner.shape)}')
-    if partner.device != pool.device:
-        raise _lib.HawkeyeHipError(f'{what}: pool on {pool.device} but partner on {partner.device}')
-    return partner.to(torch.int32).contiguous()
+    return _int_tensor(partner, (2 * pool.shape[0],), torch.int32, pool.device, what, 'partner', same_device=True)
 
 
 def api_pairs(pool, labels):
@@ -904,11 +926,7 @@ def api_pairs(pool, labels):
     ties to the lowest index, 0 where a row has no candidate.  replaces get_pairs, model/methods/APINet.py:76-91."""
     pool = _api_pool(pool.detach(), 'api_pairs')
     b, d = pool.shape
-    if labels.is_floating_point() or labels.dtype == torch.bool:
-        raise _lib.HawkeyeHipError(f'api_pairs: labels must be integers; got {labels.dtype}')
-    if tuple(labels.shape) != (b,):
-        raise _lib.HawkeyeHipError(f'api_pairs: {b} rows but labels of shape {tuple(labels.shape)}')
-    y = labels.to(device=pool.device, dtype=torch.int32).contiguous()
+    y = _int_tensor(labels, (b,), torch.int32, pool.device, 'api_pairs', 'labels')
     lib = _lib.load()
     partner = torch.empty(2 * b, dtype=torch.int32, device=pool.device)
     check(lib.hk_api_pairs(ptr(pool), ptr(y), ptr(partner), b, d, stream()), 'hk_api_pairs')
@@ -959,8 +977,7 @@ class _ApiInteract(torch.autograd.Function):
         b, d = pool.shape
         if tuple(m.shape) != (2 * b, d):
             raise _lib.HawkeyeHipError(f'api_interact: m must be [2B, D] = [{2 * b}, {d}], got {tuple(m.shape)}')
-        if m.device != pool.device:
-            raise _lib.HawkeyeHipError(f'api_interact: pool on {pool.device} but m on {m.device}')
+        _one_device('api_interact', pool.device, m)
         m = _f32c(m)
         scale = 1.0
         if masks is not None:
@@ -968,8 +985,7 @@ class _ApiInteract(torch.autograd.Function):
                 raise _lib.HawkeyeHipError(f'api_interact: keep-masks must be bool or uint8; got {masks.dtype}')
             if tuple(masks.shape) != (8 * b, d):
                 raise _lib.HawkeyeHipError(f'api_interact: keep-masks must be [8B, D] = [{8 * b}, {d}], got {tuple(masks.shape)}')
-            if masks.device != pool.device:
-                raise _lib.HawkeyeHipError(f'api_interact: pool on {pool.device} but masks on {masks.device}')
+            _one_device('api_interact', pool.device, masks)
             if not 0.0 <= drop_p < 1.0:
                 raise _lib.HawkeyeHipError(f'api_interact: drop_p must lie in [0, 1); got {drop_p}')
             masks = masks.contiguous().view(torch.uint8)
@@ -1004,18 +1020,13 @@ def _apinet_loss_args(self_logits, other_logits, labels1, labels2, what='apinet_
     if self_logits.dim() != 2 or self_logits.shape != other_logits.shape:
         raise _lib.HawkeyeHipError(f'{what}: logits of shapes {tuple(self_logits.shape)} and {tuple(other_logits.shape)}; '
                                    f'two [R, C] matrices of one shape are needed')
-    if self_logits.device != other_logits.device:
-        raise _lib.HawkeyeHipError(f'{what}: logits on {self_logits.device} and {other_logits.device}')
+    _one_device(what, self_logits.device, other_logits)
     ls, lo = _f32c(self_logits), _f32c(other_logits)
     r = ls.shape[0]
-    for y in (labels1, labels2):
-        if y.is_floating_point() or y.dtype == torch.bool:
-            raise _lib.HawkeyeHipError(f'{what}: labels must be integers; got {y.dtype}')
     if labels1.dim() != 1 or labels1.shape != labels2.shape or 2 * labels1.shape[0] != r:
         raise _lib.HawkeyeHipError(f'{what}: {r} rows need labels1 and labels2 of shape ({r // 2},) each, got '
                                    f'{tuple(labels1.shape)} and {tuple(labels2.shape)}')
-    y = torch.cat([labels1, labels2]).to(device=ls.device, dtype=torch.int32)        # on the device, no host round trip
-    return ls, lo, y
+    return ls, lo, _int_tensor(torch.cat([labels1, labels2]), (r,), torch.int32, ls.device, what, 'labels')     # one cat, one cast
 
 
 class _APINetLoss(torch.autograd.Function):
@@ -1033,15 +1044,11 @@ class _APINetLoss(torch.autograd.Function):
         ws = _ws(nws, ls.device)
         check(lib.hk_apinet_loss(ptr(ls), ptr(lo), ptr(y), label_smoothing, margin, ptr(loss), ptr(ds), ptr(do), r, c, ptr(ws),
                                  nws, stream()), 'hk_apinet_loss')
-        ctx.save_for_backward(ds, do)
-        parts = loss[1:]
-        ctx.mark_non_differentiable(parts)
-        return loss[0], parts
+        return _loss_forward(ctx, loss, (ds, do))
 
     @staticmethod
     def backward(ctx, g, _g_parts):
-        ds, do = ctx.saved_tensors
-        return ds * g, do * g, None, None, None, None
+        return _loss_backward(ctx, g, 4)
 
 
 def apinet_loss(self_logits, other_logits, labels1, labels2, label_smoothing=0.1, margin=0.05):
@@ -1057,16 +1064,6 @@ def apinet_loss_with_parts(self_logits, other_logits, labels1, labels2, label_sm
 
 
 # --------------------------------------------------------------------- NTS-Net proposals, part crops, loss
-def _nts_int(t, shape, device, what, name):
-    if t.is_floating_point() or t.dtype == torch.bool:
-        raise _lib.HawkeyeHipError(f'{what}: {name} must be integers; got {t.dtype}')
-    if tuple(t.shape) != tuple(shape):
-        raise _lib.HawkeyeHipError(f'{what}: {name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
-    if t.device != device:
-        raise _lib.HawkeyeHipError(f'{what}: {name} on {t.device} but the data on {device}')
-    return t.to(torch.int32).contiguous()
-
-
 def nts_nms(scores, anchors, topn, iou_thresh=0.25):
     """scores [B,A], anchors integer [A,4] = y0, x0, y1, x1 -> (index int64 [B,topn], boxes int32 [B,topn,4]) on the
     device, no autograd, no host round trip.  replaces hard_nms (model/methods/NTS_Net/anchors.py:63-90) and the numpy
@@ -1083,7 +1080,7 @@ def nts_nms(scores, anchors, topn, iou_thresh=0.25):
     topn = int(topn)
     if topn < 1:
         raise _lib.HawkeyeHipError(f'nts_nms: topn must be positive; got {topn}')
-    anchors = _nts_int(anchors, (a, 4), scores.device, 'nts_nms', 'anchors')
+    anchors = _int_tensor(anchors, (a, 4), torch.int32, scores.device, 'nts_nms', 'anchors', same_device=True)
     lib = _lib.load()
     index = torch.empty(b, topn, dtype=torch.int32, device=scores.device)
     boxes = torch.empty(b, topn, 4, dtype=torch.int32, device=scores.device)
@@ -1103,7 +1100,7 @@ def nts_crop_resize(images, boxes, pad, size):
     if boxes.dim() != 3 or boxes.shape[1] < 1:
         raise _lib.HawkeyeHipError(f'nts_crop_resize: boxes must be [B, N, 4], got {tuple(boxes.shape)}')
     n = boxes.shape[1]
-    boxes = _nts_int(boxes, (b, n, 4), images.device, 'nts_crop_resize', 'boxes')
+    boxes = _int_tensor(boxes, (b, n, 4), torch.int32, images.device, 'nts_crop_resize', 'boxes', same_device=True)
     oh, ow = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
     if oh < 1 or ow < 1 or int(pad) < 0:
         raise _lib.HawkeyeHipError(f'nts_crop_resize: size {size} and pad {pad} must be positive / non-negative')
@@ -1123,14 +1120,8 @@ def _nts_loss_args(raw_logits, concat_logits, part_logits, top_n_prob, labels, w
     n = part_logits.shape[1]
     if tuple(top_n_prob.shape) != (b, n):
         raise _lib.HawkeyeHipError(f'{what}: top_n_prob must be [{b}, {n}], got {tuple(top_n_prob.shape)}')
-    for t in (concat_logits, part_logits, top_n_prob):
-        if t.device != raw_logits.device:
-            raise _lib.HawkeyeHipError(f'{what}: tensors on {raw_logits.device} and {t.device}')
-    if labels.is_floating_point() or labels.dtype == torch.bool:
-        raise _lib.HawkeyeHipError(f'{what}: labels must be integers; got {labels.dtype}')
-    if tuple(labels.shape) != (b,):
-        raise _lib.HawkeyeHipError(f'{what}: {b} samples need labels of shape ({b},), got {tuple(labels.shape)}')
-    y = labels.to(device=raw_logits.device, dtype=torch.int32).contiguous()
+    _one_device(what, raw_logits.device, concat_logits, part_logits, top_n_prob)
+    y = _int_tensor(labels, (b,), torch.int32, raw_logits.device, what, 'labels')
     return _f32c(raw_logits), _f32c(concat_logits), _f32c(part_logits), _f32c(top_n_prob), y
 
 
@@ -1149,14 +1140,11 @@ class _NTSLoss(torch.autograd.Function):
         ws = _ws(nws, raw.device)
         check(lib.hk_nts_loss(ptr(raw), ptr(cat), ptr(part), ptr(prob), ptr(y), label_smoothing, ptr(loss), *[ptr(g) for g in grads],
                               b, n, c, ptr(ws), nws, stream()), 'hk_nts_loss')
-        ctx.save_for_backward(*grads)
-        parts = loss[1:]
-        ctx.mark_non_differentiable(parts)
-        return loss[0], parts
+        return _loss_forward(ctx, loss, grads)
 
     @staticmethod
     def backward(ctx, g, _g_parts):
-        return tuple(t * g for t in ctx.saved_tensors) + (None, None)
+        return _loss_backward(ctx, g, 2)
 
 
 def nts_loss(raw_logits, concat_logits, part_logits, top_n_prob, labels, label_smoothing=0.1):
@@ -1176,12 +1164,6 @@ def nts_loss_with_parts(raw_logits, concat_logits, part_logits, top_n_prob, labe
 ME_POOLS = {'max': 0, 'avg': 1}
 
 
-def _cx_map(t, shape, what, name):
-    if tuple(t.shape) != tuple(shape):
-        raise _lib.HawkeyeHipError(f'{what}: {name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
-    return _f32c(t)
-
-
 def crossx_me_bwd(d_main, d_parts, d_pooled, argmax, dz, out, gates, main, parts, pool):
     """The raw backward of `crossx_me` (hk_crossx_me_bwd): d_main [N,C,H,W], d_parts [P,N,C,H,W], d_pooled [P,N,C] and
     dz [N,C] - the gradient that reaches the squeeze GAP(out) - may each be None, meaning zero -> (d_out, d_res, d_gates).
@@ -1189,12 +1171,12 @@ def crossx_me_bwd(d_main, d_parts, d_pooled, argmax, dz, out, gates, main, parts
     lib = _lib.load()
     mode = ME_POOLS[pool]
     p, n, c, h, w = parts.shape
-    out, main, parts, gates = _cx_map(out, (n, c, h, w), 'crossx_me_bwd', 'out'), _cx_map(main, (n, c, h, w), 'crossx_me_bwd', 'main'), \
-        _f32c(parts), _cx_map(gates, (p, n, c), 'crossx_me_bwd', 'gates')
-    d_main = None if d_main is None else _cx_map(d_main, (n, c, h, w), 'crossx_me_bwd', 'd_main')
-    d_parts = None if d_parts is None else _cx_map(d_parts, (p, n, c, h, w), 'crossx_me_bwd', 'd_parts')
-    d_pooled = None if d_pooled is None else _cx_map(d_pooled, (p, n, c), 'crossx_me_bwd', 'd_pooled')
-    dz = None if dz is None else _cx_map(dz, (n, c), 'crossx_me_bwd', 'dz')
+    out, main, parts, gates = _f32_shaped(out, (n, c, h, w), 'crossx_me_bwd', 'out'), _f32_shaped(main, (n, c, h, w), 'crossx_me_bwd', 'main'), \
+        _f32c(parts), _f32_shaped(gates, (p, n, c), 'crossx_me_bwd', 'gates')
+    d_main = None if d_main is None else _f32_shaped(d_main, (n, c, h, w), 'crossx_me_bwd', 'd_main')
+    d_parts = None if d_parts is None else _f32_shaped(d_parts, (p, n, c, h, w), 'crossx_me_bwd', 'd_parts')
+    d_pooled = None if d_pooled is None else _f32_shaped(d_pooled, (p, n, c), 'crossx_me_bwd', 'd_pooled')
+    dz = None if dz is None else _f32_shaped(dz, (n, c), 'crossx_me_bwd', 'dz')
     d_out, d_res, d_gates = torch.empty_like(out), torch.empty_like(out), torch.empty_like(gates)
     check(lib.hk_crossx_me_bwd(ptr(d_main), ptr(d_parts), ptr(d_pooled), ptr(argmax), ptr(dz), ptr(out), ptr(gates), ptr(main), ptr(parts),
                                ptr(d_out), ptr(d_res), ptr(d_gates), p, n, c, h * w, mode, stream()), 'hk_crossx_me_bwd')
@@ -1213,7 +1195,7 @@ class _CrossXME(torch.autograd.Function):
         if out.dim() != 4 or min(out.shape) < 1:
             raise _lib.HawkeyeHipError(f'crossx_me: out must be [N, C, H, W], got {tuple(out.shape)}')
         n, c, h, w = out.shape
-        res = _cx_map(res, (n, c, h, w), 'crossx_me', 'res')
+        res = _f32_shaped(res, (n, c, h, w), 'crossx_me', 'res')
         if gates.dim() != 3 or tuple(gates.shape[1:]) != (n, c) or not 1 <= gates.shape[0] <= 3:
             raise _lib.HawkeyeHipError(f'crossx_me: gates must be [P, N, C] = [1..3, {n}, {c}], got {tuple(gates.shape)}')
         gates = _f32c(gates)
@@ -1278,8 +1260,7 @@ def crossx_up_add(a, b):
         raise _lib.HawkeyeHipError(f'crossx_up_add: two [N, C, H, W] maps of one N and C are needed, got {tuple(a.shape)} and {tuple(b.shape)}')
     if a.shape[2] % b.shape[2] or a.shape[3] % b.shape[3]:
         raise _lib.HawkeyeHipError(f'crossx_up_add: the size {tuple(a.shape[2:])} is no whole multiple of {tuple(b.shape[2:])}')
-    if a.device != b.device:
-        raise _lib.HawkeyeHipError(f'crossx_up_add: tensors on {a.device} and {b.device}')
+    _one_device('crossx_up_add', a.device, b)
     return _CrossXUpAdd.apply(a, b)
 
 
@@ -1288,8 +1269,7 @@ def _cx_features(feats, b, device, what, name):
     t = torch.stack([f.reshape(f.shape[0], -1) for f in feats]) if isinstance(feats, (list, tuple)) else feats
     if t.dim() != 3 or t.shape[1] != b or not 1 <= t.shape[0] <= 3 or t.shape[2] < 1:
         raise _lib.HawkeyeHipError(f'{what}: {name} must be 1 to 3 parts of [{b}, C] features, got {tuple(t.shape)}')
-    if t.device != device:
-        raise _lib.HawkeyeHipError(f'{what}: tensors on {device} and {t.device}')
+    _one_device(what, device, t)
     return t
 
 
@@ -1310,14 +1290,11 @@ class _CrossXLoss(torch.autograd.Function):
         ws = _ws(nws, ulti.device)
         check(lib.hk_crossx_loss(ptr(ulti), ptr(plty), ptr(cmbn), ptr(labels), ptr(f_ulti), ptr(f_plty), ptr(f_cmbn), gamma[0], gamma[1],
                                  gamma[2], 1.0, ptr(loss), *[ptr(g) for g in grads], b, k, p, *cs, ptr(ws), nws, stream()), 'hk_crossx_loss')
-        ctx.save_for_backward(*grads)
-        terms = loss[1:]
-        ctx.mark_non_differentiable(terms)
-        return loss[0], terms
+        return _loss_forward(ctx, loss, grads)
 
     @staticmethod
     def backward(ctx, g, _g_terms):
-        return tuple(t * g for t in ctx.saved_tensors) + (None, None)
+        return _loss_backward(ctx, g, 2)
 
 
 def _crossx_loss_args(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma, what='crossx_loss'):
@@ -1327,20 +1304,15 @@ def _crossx_loss_args(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels,
     b = ulti.shape[0]
     if b < 2:                                              # the reference's squeeze() drops the batch axis at B = 1 and fails
         raise _lib.HawkeyeHipError(f'{what}: the batch must hold at least 2 samples, got {b}')
-    for t in (plty, cmbn):
-        if t.device != ulti.device:
-            raise _lib.HawkeyeHipError(f'{what}: tensors on {ulti.device} and {t.device}')
+    _one_device(what, ulti.device, plty, cmbn)
     feats = [_cx_features(f, b, ulti.device, what, n) for f, n in ((ulti_ftrs, 'ulti_ftrs'), (plty_ftrs, 'plty_ftrs'), (cmbn_ftrs, 'cmbn_ftrs'))]
     if len({f.shape[0] for f in feats}) != 1:
         raise _lib.HawkeyeHipError(f'{what}: the three feature lists hold {[f.shape[0] for f in feats]} parts')
-    if labels.is_floating_point() or labels.dtype == torch.bool:
-        raise _lib.HawkeyeHipError(f'{what}: labels must be integers; got {labels.dtype}')
-    if tuple(labels.shape) != (b,):
-        raise _lib.HawkeyeHipError(f'{what}: {b} samples need labels of shape ({b},), got {tuple(labels.shape)}')
+    y = _int_tensor(labels, (b,), torch.int64, ulti.device, what, 'labels')
     gamma = tuple(float(v) for v in gamma)
     if len(gamma) != 3:
         raise _lib.HawkeyeHipError(f'{what}: gamma must hold three values (ulti, plty, cmbn), got {gamma}')
-    return feats, labels.to(device=ulti.device, dtype=torch.int64).contiguous(), gamma
+    return feats, y, gamma
 
 
 def crossx_loss_with_terms(ulti, plty, cmbn, ulti_ftrs, plty_ftrs, cmbn_ftrs, labels, gamma):
@@ -1368,23 +1340,21 @@ def _dcl_head_args(x, weight, bias, what):
         raise _lib.HawkeyeHipError(f'{what}: weight must hold {c} values ([1, {c}, 1, 1] or [{c}]), got {tuple(weight.shape)}')
     if bias.numel() != 1:
         raise _lib.HawkeyeHipError(f'{what}: bias must hold one value, got {tuple(bias.shape)}')
-    for t in (weight, bias):
-        if t.device != x.device:
-            raise _lib.HawkeyeHipError(f'{what}: tensors on {x.device} and {t.device}')
+    _one_device(what, x.device, weight, bias)
     return _f32c(x), _f32c(weight).reshape(c), _f32c(bias).reshape(1)
 
 
 def dcl_head_bwd(x, weight, mask, d_pooled, d_mask, need=(True, True, True)):
     """The raw backward of `dcl_head` (hk_dcl_head_bwd): x [B,C,H,W], weight [C], the saved mask [B,M]; d_pooled [B,C] and
     d_mask [B,M] may each be None, meaning zero -> (dx, dw [C], dbias [1]), None where `need` says so.  No autograd."""
-    lib = _lib.bind(_lib.load())
+    lib = _lib.load()
     x, weight, mask = _f32c(x), _f32c(weight).reshape(-1), _f32c(mask)
     b, c, h, w = x.shape
     m = (h // 2) * (w // 2)
     if tuple(mask.shape) != (b, m):
         raise _lib.HawkeyeHipError(f'dcl_head_bwd: mask must have the shape {(b, m)}, got {tuple(mask.shape)}')
-    d_pooled = None if d_pooled is None else _cx_map(d_pooled, (b, c), 'dcl_head_bwd', 'd_pooled')
-    d_mask = None if d_mask is None else _cx_map(d_mask, (b, m), 'dcl_head_bwd', 'd_mask')
+    d_pooled = None if d_pooled is None else _f32_shaped(d_pooled, (b, c), 'dcl_head_bwd', 'd_pooled')
+    d_mask = None if d_mask is None else _f32_shaped(d_mask, (b, m), 'dcl_head_bwd', 'd_mask')
     dx = torch.empty_like(x) if need[0] else None
     dw = torch.empty(c, dtype=torch.float32, device=x.device) if need[1] else None
     dbias = torch.empty(1, dtype=torch.float32, device=x.device) if need[2] else None
@@ -1400,7 +1370,7 @@ class _DCLHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        lib = _lib.bind(_lib.load())
+        lib = _lib.load()
         ctx.wshape, ctx.bshape = weight.shape, bias.shape
         x, weight, bias = _dcl_head_args(x, weight, bias, 'dcl_head')
         b, c, h, w = x.shape
@@ -1434,7 +1404,7 @@ class _DCLLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, swap_logits, mask, labels, labels_swap, law, coef, smoothing):
-        lib = _lib.bind(_lib.load())
+        lib = _lib.load()
         logits, swap_logits, mask = _f32c(logits), _f32c(swap_logits), _f32c(mask)
         n, k = logits.shape
         loss = torch.empty(4, dtype=torch.float32, device=logits.device)
@@ -1442,14 +1412,11 @@ class _DCLLoss(torch.autograd.Function):
         check(lib.hk_dcl_loss(ptr(logits), ptr(swap_logits), ptr(mask), ptr(labels), ptr(labels_swap), ptr(law), coef[0], coef[1], coef[2],
                               smoothing, 1.0, ptr(loss), *[ptr(g) for g in grads], n, k, swap_logits.shape[1], mask.shape[1], stream()),
               'hk_dcl_loss')
-        ctx.save_for_backward(*grads)
-        terms = loss[1:]
-        ctx.mark_non_differentiable(terms)
-        return loss[0], terms
+        return _loss_forward(ctx, loss, grads)
 
     @staticmethod
     def backward(ctx, g, _g_terms):
-        return tuple(t * g for t in ctx.saved_tensors) + (None,) * 5
+        return _loss_backward(ctx, g, 5)
 
 
 def _dcl_loss_args(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha, beta, gamma, what='dcl_loss'):
@@ -1458,21 +1425,14 @@ def _dcl_loss_args(logits, swap_logits, mask, labels, labels_swap, swap_law, alp
         raise _lib.HawkeyeHipError(f'{what}: logits [N, K], swap logits [N, S] and a mask [N, M] of one N are needed, got '
                                    f'{tuple(logits.shape)}, {tuple(swap_logits.shape)} and {tuple(mask.shape)}')
     n = logits.shape[0]
-    for t in (swap_logits, mask):
-        if t.device != logits.device:
-            raise _lib.HawkeyeHipError(f'{what}: tensors on {logits.device} and {t.device}')
-    for name, y in (('labels', labels), ('labels_swap', labels_swap)):
-        if y.is_floating_point() or y.dtype == torch.bool:
-            raise _lib.HawkeyeHipError(f'{what}: {name} must be integers; got {y.dtype}')
-        if tuple(y.shape) != (n,):
-            raise _lib.HawkeyeHipError(f'{what}: {n} samples need {name} of shape ({n},), got {tuple(y.shape)}')
+    dev = logits.device
+    _one_device(what, dev, swap_logits, mask)
+    y, ys = (_int_tensor(t, (n,), torch.int64, dev, what, name) for t, name in ((labels, 'labels'), (labels_swap, 'labels_swap')))
     if tuple(swap_law.shape) != tuple(mask.shape):
         raise _lib.HawkeyeHipError(f'{what}: swap_law must have the mask\'s shape {tuple(mask.shape)}, got {tuple(swap_law.shape)}')
     if not swap_law.is_floating_point():
         raise _lib.HawkeyeHipError(f'{what}: swap_law must be floating point; got {swap_law.dtype}')
-    dev = logits.device
-    return (labels.to(device=dev, dtype=torch.int64).contiguous(), labels_swap.to(device=dev, dtype=torch.int64).contiguous(),
-            swap_law.to(device=dev, dtype=torch.float32).contiguous(), (float(alpha), float(beta), float(gamma)))
+    return y, ys, swap_law.to(device=dev, dtype=torch.float32).contiguous(), (float(alpha), float(beta), float(gamma))
 
 
 def dcl_loss_with_terms(logits, swap_logits, mask, labels, labels_swap, swap_law, alpha=1.0, beta=1.0, gamma=1.0, label_smoothing=0.1):
@@ -1504,15 +1464,14 @@ def dcl_swap_law(u8_unswap, u8_swap, grid=(7, 7)):
     of the swapped image (row-major) `index` names the patch of the unswapped image with the nearest sum of band means -
     every decision as the reference takes it in float64, the lowest index on ties - and law = (index - P // 2) / P.  No
     gradient."""
-    lib = _lib.bind(_lib.load())
+    lib = _lib.load()
     gx, gy = (int(g) for g in grid)
     for name, t in (('u8_unswap', u8_unswap), ('u8_swap', u8_swap)):
         if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
             raise _lib.HawkeyeHipError(f'dcl_swap_law: {name} must be uint8 [N, H, W, 3], got {t.dtype} {tuple(t.shape)}')
     if u8_unswap.shape != u8_swap.shape:
         raise _lib.HawkeyeHipError(f'dcl_swap_law: two batches of one shape are needed, got {tuple(u8_unswap.shape)} and {tuple(u8_swap.shape)}')
-    if u8_unswap.device != u8_swap.device:
-        raise _lib.HawkeyeHipError(f'dcl_swap_law: tensors on {u8_unswap.device} and {u8_swap.device}')
+    _one_device('dcl_swap_law', u8_unswap.device, u8_swap)
     n, h, w, _ = u8_unswap.shape
     if gx < 1 or gy < 1:
         raise _lib.HawkeyeHipError(f'dcl_swap_law: grid must hold two positive counts, got {grid}')

@@ -149,7 +149,7 @@ def check_head_refused(device):
         assert '2 x 2' in str(e)
     else:
         raise AssertionError('H = 1 must be refused')
-    lib = _lib.bind(_lib.load())
+    lib = _lib.load()
     pooled, mask, ws = torch.zeros(1, 3, device=device), torch.zeros(1, 4, device=device), torch.zeros(4096, dtype=torch.uint8, device=device)
     assert lib.hk_dcl_head_fwd_ws_bytes(1, 3, 1, 4) == 0 and lib.hk_dcl_head_bwd_ws_bytes(1, 3, 4, 1) == 0
     rc = lib.hk_dcl_head_fwd(HF.ptr(x), HF.ptr(w), HF.ptr(bias), HF.ptr(pooled), HF.ptr(mask), 1, 3, 1, 4, HF.ptr(ws), 4096, HF.stream())
@@ -196,7 +196,7 @@ def check_loss_scaling(case, device, weight=4.0):
     leaves, rest = loss_tensors(case, device, grad=False)
     loss = torch.empty(4, device=device)
     grads = [torch.empty_like(t) for t in leaves]
-    rc = _lib.bind(_lib.load()).hk_dcl_loss(*[HF.ptr(t) for t in leaves], *[HF.ptr(t) for t in rest], *T.COEF, T.SMOOTHING, weight, HF.ptr(loss),
+    rc = _lib.load().hk_dcl_loss(*[HF.ptr(t) for t in leaves], *[HF.ptr(t) for t in rest], *T.COEF, T.SMOOTHING, weight, HF.ptr(loss),
                                  *[HF.ptr(g) for g in grads], case['N'], case['K'], case['S'], case['M'], HF.stream())
     assert rc == 0 and np_(loss).tobytes() == one['loss'].tobytes()
     for name, g in zip(T.LOSS_RESULTS[1:], grads):
@@ -275,6 +275,6 @@ def check_law_refused(device):
         raise AssertionError('a 3 x 3 image has no 7 x 7 patches')
     bounds = torch.zeros(8, dtype=torch.int32, device=device)
     index, law = torch.zeros(1, 49, dtype=torch.int32, device=device), torch.zeros(1, 49, device=device)
-    rc = _lib.bind(_lib.load()).hk_dcl_swap_law(HF.ptr(tiny), HF.ptr(tiny), HF.ptr(bounds), HF.ptr(bounds), HF.ptr(index), HF.ptr(law), 1, 3, 3, 7, 7,
+    rc = _lib.load().hk_dcl_swap_law(HF.ptr(tiny), HF.ptr(tiny), HF.ptr(bounds), HF.ptr(bounds), HF.ptr(index), HF.ptr(law), 1, 3, 3, 7, 7,
                                      HF.stream())
     assert rc == _lib.HK_ERR_UNSUPPORTED

@@ -22,12 +22,7 @@ _emu = None
 def load_emu():
     global _emu
     if _emu is None:
-        lib = ctypes.CDLL(build_emu.build())
-        for name, (res, args) in _lib.SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _emu = lib
+        _emu = _lib.attach(ctypes.CDLL(build_emu.build()))
     return _emu
 
 

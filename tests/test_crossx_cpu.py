@@ -166,7 +166,7 @@ def test_host_side_queries_need_no_gpu():
     assert lib.hk_crossx_loss_ws_bytes(1, 200, 2, 2048, 1024, 1024) == 0 and lib.hk_crossx_loss_ws_bytes(8, 200, 4, 8, 8, 8) == 0
     assert sorted(n for n in _lib.SIGNATURES if n.startswith('hk_crossx_')) == [
         'hk_crossx_loss', 'hk_crossx_loss_ws_bytes', 'hk_crossx_me_bwd', 'hk_crossx_me_fwd', 'hk_crossx_up_add_bwd', 'hk_crossx_up_add_fwd']
-    assert len(_lib.SIGNATURES) == 98
+    assert len(_lib.SIGNATURES) == 104
 
 
 def test_synthetic_yaml_parses_and_names_the_plugin():

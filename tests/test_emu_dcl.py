@@ -94,7 +94,7 @@ def p(t):
 
 def test_abi_errors():
     from hawkeye_amd import _lib
-    lib = _lib.bind(_lib.load())
+    lib = _lib.load()
     z = ctypes.c_void_p(0)
     bad, big, short = _lib.HK_ERR_BAD_ARG, _lib.HK_ERR_UNSUPPORTED, _lib.HK_ERR_WORKSPACE
     B, C, H, W = 2, 5, 4, 6

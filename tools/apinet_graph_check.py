@@ -22,6 +22,7 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 import apinet_inputs as A  # noqa: E402
+from graph_capture import Step as _Step, main, replays_match  # noqa: E402
 
 N_CLASSES, N_SAMPLES, D, HIDDEN = A.HEAD_CASES[-1]
 
@@ -45,7 +46,7 @@ def device_case(seed, dev):
     return torch.from_numpy(x.mean((2, 3))).to(dev), torch.from_numpy(y).to(dev)
 
 
-class Step:
+class Step(_Step):
     """Forward + backward of head and loss on static tensors; `capture()` turns it into one graph."""
 
     def __init__(self, net, dev):
@@ -53,7 +54,6 @@ class Step:
         self.net, self.crit = net, APINetLoss(None)
         self.pool = torch.zeros(N_CLASSES * N_SAMPLES, D, device=dev, requires_grad=True)
         self.y = torch.zeros(N_CLASSES * N_SAMPLES, dtype=torch.int64, device=dev)
-        self.graph = None
 
     def load(self, pool, y):
         with torch.no_grad():
@@ -74,42 +74,12 @@ class Step:
     def results(self, loss):
         return [loss, self.pool.grad, self.net.map1.weight.grad, self.net.fc.weight.grad, self.net.fc.bias.grad]
 
-    def capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # warm-up off the capture
-            for _ in range(3):
-                self.clear()
-                self.run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.clear()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss = self.run()
-
-    def replay(self):
-        self.graph.replay()
-        return self.results(self.loss)
-
 
 def check(dev):
-    net = head_only(dev).eval()
-    cap, eager = Step(net, dev), Step(head_only(dev).eval(), dev)
-    cap.load(*device_case(1, dev))
-    cap.capture()
     names = ('loss', 'dpool', 'map1.weight.grad', 'fc.weight.grad', 'fc.bias.grad')
-    for seed in (11, 12, 13):
-        case = device_case(seed, dev)
-        eager.load(*case)
-        eager.clear()
-        want = [t.clone() for t in eager.results(eager.run())]
-        cap.load(*case)
-        got = cap.replay()
-        torch.cuda.synchronize()
-        for name, w, g in zip(names, want, got):
-            if not torch.equal(w, g) or not torch.isfinite(g).all():
-                print(f'replay with seed {seed}: {name} differs from the eager result')
-                return 1
+    if not replays_match(Step(head_only(dev).eval(), dev), Step(head_only(dev).eval(), dev), lambda seed: device_case(seed, dev), names,
+                         load=lambda step, case: step.load(*case)):
+        return 1
     train = Step(head_only(dev).train(), dev)
     train.load(*device_case(2, dev))
     train.capture()
@@ -127,9 +97,4 @@ def check(dev):
 
 
 if __name__ == '__main__':
-    if not torch.cuda.is_available():
-        print('apinet_graph_check needs an MI355X')
-        sys.exit(2)
-    device = torch.device('cuda', 0)
-    torch.cuda.set_device(device)
-    sys.exit(check(device))
+    main('apinet_graph_check', check)

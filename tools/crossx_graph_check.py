@@ -22,6 +22,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import crossx_inputs as T  # noqa: E402
+from graph_capture import Step as _Step, main, replays_match  # noqa: E402
 
 B, P, K = 8, 2, 200
 SHAPES = dict(out3=(B, 1024, 28, 28), res3=(B, 1024, 28, 28), gates3=(P, B, 1024), out4=(B, 2048, 14, 14), res4=(B, 2048, 14, 14),
@@ -38,7 +39,7 @@ def device_case(seed, dev):
     return case
 
 
-class Step:
+class Step(_Step):
     """The head on static tensors; `capture()` turns it into one graph."""
 
     def __init__(self, dev):
@@ -46,16 +47,6 @@ class Step:
         self.HF = HF
         self.static = {name: torch.zeros(*shape, device=dev).requires_grad_(True) for name, shape in SHAPES.items()}
         self.static['y'] = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.graph = None
-
-    def load(self, case):
-        with torch.no_grad():
-            for k, v in case.items():
-                self.static[k].copy_(v)
-
-    def clear(self):
-        for t in self.static.values():
-            t.grad = None
 
     def run(self):
         s, HF = self.static, self.HF
@@ -69,54 +60,16 @@ class Step:
     def results(self, out):
         return out + [self.static[name].grad for name in SHAPES]
 
-    def capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # warm-up off the capture
-            for _ in range(3):
-                self.clear()
-                self.run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.clear()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = self.run()
-
-    def replay(self):
-        self.graph.replay()
-        return self.results(self.out)
-
 
 NAMES = ('loss', 'loss terms') + tuple('d ' + name for name in SHAPES)
 
 
 def check(dev):
-    cap, eager = Step(dev), Step(dev)
-    cap.load(device_case(1, dev))
-    cap.capture()
-    for seed in (11, 12, 13):
-        case = device_case(seed, dev)
-        eager.load(case)
-        eager.clear()
-        want = [t.clone() for t in eager.results(eager.run())]
-        cap.load(case)
-        got = cap.replay()
-        torch.cuda.synchronize()
-        for name, w, g in zip(NAMES, want, got):
-            if not torch.equal(w, g) or not torch.isfinite(g).all():
-                print(f'replay with seed {seed}: {name} differs from the eager result or is not finite')
-                return 1
-        if not all(g.any() for g in got):
-            print(f'replay with seed {seed}: an empty result')
-            return 1
+    if not replays_match(Step(dev), Step(dev), lambda seed: device_case(seed, dev), NAMES):
+        return 1
     print('crossx_graph_check ok: 3 replays bit-identical to eager (two ME blocks, upsample + add, loss, forward + backward)')
     return 0
 
 
 if __name__ == '__main__':
-    if not torch.cuda.is_available():
-        print('crossx_graph_check needs an MI355X')
-        sys.exit(2)
-    device = torch.device('cuda', 0)
-    torch.cuda.set_device(device)
-    sys.exit(check(device))
+    main('crossx_graph_check', check)

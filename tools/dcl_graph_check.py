@@ -20,6 +20,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import dcl_inputs as T  # noqa: E402
+from graph_capture import Step as _Step, main, replays_match  # noqa: E402
 
 B, K, SIDE, GRID = 8, 200, 448, (7, 7)
 SHAPES = dict(x=(2 * B, 2048, 14, 14), w=(1, 2048, 1, 1), bias=(1,), cls=(K, 2048), swap=(2, 2048))
@@ -36,8 +37,8 @@ def device_case(seed, dev):
     return case
 
 
-class Step:
-    """The head on static tensors; `capture()` turns it into one graph."""
+class Step(_Step):
+    """The head on static tensors; `capture()` turns it into one graph (its warm-up also uploads the patch bounds)."""
 
     def __init__(self, dev):
         import hawkeye_amd.functional as HF
@@ -47,16 +48,6 @@ class Step:
         self.static.update(un=torch.zeros(B, SIDE, SIDE, 3, dtype=torch.uint8, device=dev), sw=torch.zeros(B, SIDE, SIDE, 3, dtype=torch.uint8, device=dev),
                            y=torch.zeros(2 * B, dtype=torch.int64, device=dev), ys=torch.zeros(2 * B, dtype=torch.int64, device=dev))
         self.ramp = dcl_law_ramp(GRID[0] * GRID[1]).to(dev)
-        self.graph = None
-
-    def load(self, case):
-        with torch.no_grad():
-            for k, v in case.items():
-                self.static[k].copy_(v)
-
-    def clear(self):
-        for t in self.static.values():
-            t.grad = None
 
     def run(self):
         s, HF = self.static, self.HF
@@ -70,57 +61,20 @@ class Step:
     def results(self, out):
         return out + [self.static[name].grad for name in SHAPES]
 
-    def capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # warm-up off the capture (it also uploads the patch bounds)
-            for _ in range(3):
-                self.clear()
-                self.run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.clear()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = self.run()
-
-    def replay(self):
-        self.graph.replay()
-        return self.results(self.out)
-
 
 NAMES = ('law index', 'loss', 'loss terms') + tuple('d ' + name for name in SHAPES)
 
 
 def check(dev):
-    cap, eager = Step(dev), Step(dev)
-    cap.load(device_case(1, dev))
-    cap.capture()
-    for seed in (11, 12, 13):
-        case = device_case(seed, dev)
-        eager.load(case)
-        eager.clear()
-        want = [t.clone() for t in eager.results(eager.run())]
-        cap.load(case)
-        got = cap.replay()
-        torch.cuda.synchronize()
-        for name, w, g in zip(NAMES, want, got):
-            if not torch.equal(w, g) or not torch.isfinite(g.float()).all():
-                print(f'replay with seed {seed}: {name} differs from the eager result or is not finite')
-                return 1
-        if not all(g.any() for g in got):
-            print(f'replay with seed {seed}: an empty result')
-            return 1
+    def permutation(got):
         if sorted(got[0][0].tolist()) != list(range(49)):
-            print(f'replay with seed {seed}: the law of a patch permutation is no permutation')
-            return 1
+            return 'the law of a patch permutation is no permutation'
+
+    if not replays_match(Step(dev), Step(dev), lambda seed: device_case(seed, dev), NAMES, extra=permutation):
+        return 1
     print('dcl_graph_check ok: 3 replays bit-identical to eager (swap law, head, two classifiers, loss, forward + backward)')
     return 0
 
 
 if __name__ == '__main__':
-    if not torch.cuda.is_available():
-        print('dcl_graph_check needs an MI355X')
-        sys.exit(2)
-    device = torch.device('cuda', 0)
-    torch.cuda.set_device(device)
-    sys.exit(check(device))
+    main('dcl_graph_check', check)

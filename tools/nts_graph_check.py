@@ -21,6 +21,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import nts_inputs as T  # noqa: E402
+from graph_capture import Step as _Step, main, replays_match  # noqa: E402
 
 B, N, C, SIZE = 4, 6, 200, 224
 
@@ -34,7 +35,7 @@ def device_case(seed, anchors, dev):
                 y=torch.from_numpy(y).to(dev))
 
 
-class Step:
+class Step(_Step):
     """The head on static tensors; `capture()` turns it into one graph."""
 
     def __init__(self, anchors, dev):
@@ -44,16 +45,6 @@ class Step:
         z = lambda *s: torch.zeros(*s, device=dev)
         self.static = dict(images=z(B, 3, SIZE, SIZE), scores=z(B, len(anchors)).requires_grad_(True), raw=z(B, C).requires_grad_(True),
                            cat=z(B, C).requires_grad_(True), part=z(B, N, C).requires_grad_(True), y=torch.zeros(B, dtype=torch.int64, device=dev))
-        self.graph = None
-
-    def load(self, case):
-        with torch.no_grad():
-            for k, v in case.items():
-                self.static[k].copy_(v)
-
-    def clear(self):
-        for t in self.static.values():
-            t.grad = None
 
     def run(self):
         s = self.static
@@ -68,55 +59,18 @@ class Step:
         s = self.static
         return out + [s['scores'].grad, s['raw'].grad, s['cat'].grad, s['part'].grad]
 
-    def capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # warm-up off the capture
-            for _ in range(3):
-                self.clear()
-                self.run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.clear()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = self.run()
-
-    def replay(self):
-        self.graph.replay()
-        return self.results(self.out)
-
 
 NAMES = ('index', 'boxes', 'top_n_prob', 'crops', 'loss', 'loss terms', 'd scores', 'd raw', 'd concat', 'd part')
 
 
 def check(dev):
     anchors = T.load()['anchors_224']
-    cap, eager = Step(anchors, dev), Step(anchors, dev)
-    cap.load(device_case(1, anchors, dev))
-    cap.capture()
-    for seed in (11, 12, 13):
-        case = device_case(seed, anchors, dev)
-        eager.load(case)
-        eager.clear()
-        want = [t.clone() for t in eager.results(eager.run())]
-        cap.load(case)
-        got = cap.replay()
-        torch.cuda.synchronize()
-        for name, w, g in zip(NAMES, want, got):
-            if not torch.equal(w, g) or not (g.dtype.is_floating_point is False or torch.isfinite(g).all()):
-                print(f'replay with seed {seed}: {name} differs from the eager result')
-                return 1
-        if not got[6].any() or not got[3].any():
-            print(f'replay with seed {seed}: an empty result')
-            return 1
+    if not replays_match(Step(anchors, dev), Step(anchors, dev), lambda seed: device_case(seed, anchors, dev), NAMES,
+                         nonempty=('d scores', 'crops')):
+        return 1
     print('nts_graph_check ok: 3 replays bit-identical to eager (nms, gather, crops, loss forward + backward)')
     return 0
 
 
 if __name__ == '__main__':
-    if not torch.cuda.is_available():
-        print('nts_graph_check needs an MI355X')
-        sys.exit(2)
-    device = torch.device('cuda', 0)
-    torch.cuda.set_device(device)
-    sys.exit(check(device))
+    main('nts_graph_check', check)

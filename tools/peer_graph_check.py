@@ -26,6 +26,7 @@ for p in (ROOT, os.path.join(ROOT, 'tests', 'golden')):
 import torch  # noqa: E402
 
 import hawkeye_amd.functional as HF  # noqa: E402
+from graph_capture import Step, main, replays_match  # noqa: E402
 from hawkeye_amd import _lib  # noqa: E402
 from peer_inputs import peer_inputs  # noqa: E402
 
@@ -64,57 +65,29 @@ def eager(l1, l2, y, drop_rate, loss_fn=None):
     return loss_1.detach(), loss_2.detach(), a.grad, b.grad
 
 
-class Captured:
-    """Forward + backward of the loss as one graph on static tensors."""
+class PeerStep(Step):
+    """Forward + backward of the loss on static tensors; `capture()` turns it into one graph."""
 
     def __init__(self, n, c, drop_rate, dev):
-        self.l1 = torch.zeros(n, c, device=dev, requires_grad=True)
-        self.l2 = torch.zeros(n, c, device=dev, requires_grad=True)
-        self.y = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.static = dict(l1=torch.zeros(n, c, device=dev, requires_grad=True), l2=torch.zeros(n, c, device=dev, requires_grad=True),
+                           y=torch.zeros(n, dtype=torch.int64, device=dev))
         self.drop_rate = drop_rate
-        seed = device_case(1, n, c, dev)
-        self.load(*seed)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # warm-up off the capture
-            for _ in range(3):
-                self.l1.grad = self.l2.grad = None
-                self.step()
-        torch.cuda.current_stream().wait_stream(side)
-        self.l1.grad = self.l2.grad = None
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss_1, self.loss_2 = self.step()
 
-    def step(self):
-        loss_1, loss_2 = HF.peer_learning_loss(self.l1, self.l2, self.y, self.drop_rate)
+    def run(self):
+        s = self.static
+        loss_1, loss_2 = HF.peer_learning_loss(s['l1'], s['l2'], s['y'], self.drop_rate)
         (loss_1 + loss_2).backward()
-        return loss_1.detach(), loss_2.detach()
+        return [loss_1.detach(), loss_2.detach()]
 
-    def load(self, l1, l2, y):
-        with torch.no_grad():
-            self.l1.copy_(l1)
-            self.l2.copy_(l2)
-            self.y.copy_(y)
-
-    def replay(self):
-        self.graph.replay()
-        return self.loss_1, self.loss_2, self.l1.grad, self.l2.grad
+    def results(self, out):
+        return out + [self.static['l1'].grad, self.static['l2'].grad]
 
 
 def check(dev):
     n, c, drop_rate = 64, 200, 0.35
-    cap = Captured(n, c, drop_rate, dev)
-    for seed in (11, 12, 13):
-        case = device_case(seed, n, c, dev)
-        want = [t.clone() for t in eager(*case, drop_rate)]
-        cap.load(*case)
-        got = cap.replay()
-        torch.cuda.synchronize()
-        for name, w, g in zip(('loss_1', 'loss_2', 'dl1', 'dl2'), want, got):
-            if not torch.equal(w, g):
-                print(f'replay with seed {seed}: {name} differs from the eager result')
-                return 1
+    case = lambda seed: dict(zip(('l1', 'l2', 'y'), device_case(seed, n, c, dev)))      # noqa: E731
+    if not replays_match(PeerStep(n, c, drop_rate, dev), PeerStep(n, c, drop_rate, dev), case, ('loss_1', 'loss_2', 'dl1', 'dl2')):
+        return 1
     print('peer_graph_check ok: 3 replays bit-identical to eager')
     return 0
 
@@ -124,8 +97,9 @@ def timing(dev, out):
     rows = []
     for n, c in ((8, 200), (16, 200), (64, 200)):
         case = device_case(100 + n, n, c, dev)
-        cap = Captured(n, c, drop_rate, dev)
-        cap.load(*case)
+        cap = PeerStep(n, c, drop_rate, dev)
+        cap.load(dict(zip(('l1', 'l2', 'y'), case)))
+        cap.capture()
 
         fused = lambda: eager(*case, drop_rate)                                           # noqa: E731
         variants = {'aten_us': (0, lambda: eager(*case, drop_rate, aten_peer_loss)), 'general_us': (1, fused),
@@ -190,9 +164,4 @@ if __name__ == '__main__':
     ap.add_argument('--time', action='store_true')
     ap.add_argument('--out', default='')
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        print('peer_graph_check needs an MI355X')
-        sys.exit(2)
-    device = torch.device('cuda', 0)
-    torch.cuda.set_device(device)
-    sys.exit(timing(device, args.out) if args.time else check(device))
+    main('peer_graph_check', lambda device: timing(device, args.out) if args.time else check(device))
