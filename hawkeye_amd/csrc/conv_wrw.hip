@@ -23,6 +23,36 @@
 //              image are never used
 //   result   = every workgroup writes its 64 x 576 partial; partial_sum_kernel adds the partials of an element in a fixed order
 //              (no atomics, no zero-fill: the same input gives the same bits)
+//
+// Split form (conv3x3_wrw_split_kernel, knob wrw_split): the fp32 form runs at 92 % of the fp32 matrix pipe, and the chip has no xf32,
+// but its bf16 pipe is 16 x the fp32 one.  Every x and dy value is split, once per element per workgroup on its way from registers to
+// LDS, into hi = bf16_rn(a), mid = bf16_rn(a - hi), lo = bf16_rn(a - hi - mid) (both differences exact in fp32; a = hi + mid + lo
+// to 2^-27 |a|; zeros stay zeros), and a tap's product is the six bf16 MFMAs of first and second order - hi hi, hi mid, mid hi,
+// hi lo, lo hi, mid mid - into the same nine fp32 accumulators: per 16 pixels and wave 9 x 6 v_mfma_f32_32x32x16_bf16 = 1728 pipe
+// cycles where the fp32 form takes 9 x 8 v_mfma_f32_32x32x2_f32 = 4608.  Same jobs, ring, borders, partial results and finish.
+//   numerics = the dropped products (mid lo, lo mid, lo lo) are below 2^-24 |x| |dy|: at most 3.9e-8 S from float64, S = sum |x| |dy|,
+//              1.1 - 1.3e-7 S with the fp32 accumulation - what a plain fp32 evaluation gives (tests: the fp32 form's 1e-6 S bound).
+//              Dropping the second order (three MFMAs) gives 1e-6 - 2e-5 S.  Domain: finite inputs, |a| < 2^127, zero or no smaller
+//              than about 2^-100 (below, the low pieces reach bf16 subnormals; whether the bf16 MFMA flushes them is unmeasured).  A
+//              non-finite input makes every dW element it touches non-finite: inf splits into (inf, NaN, NaN), so NaN where the fp32
+//              form may give +-inf.
+//   operands = the instruction wants 8 consecutive k (pixels) of one channel per lane, NHWC has the channel contiguous: LDS keeps
+//              [pixel][channel] bf16 planes, one per piece and per 32-channel half (a wave's A or B tile is one half), 64 bytes a
+//              pixel, written with 8-byte vector stores (a thread's float4 = 4 channels of one pixel, per piece), and read with the
+//              transposing ds_read_b64_tr_b16: a 16-lane group fetches 4 pixels x 16 channels and each lane gets the 4 pixels of its
+//              channel; two reads make a fragment.  A tap's shift kw is 64 bytes in the instruction's offset field.
+//   banks    = a 32-lane half of a transposing read covers 4 consecutive pixels x 32 channels = 256 contiguous bytes of a plane - one
+//              whole row of the 64 banks whatever pixel it starts at, so every operand read is conflict-free at any kw (with 64-channel
+//              rows, 128 bytes a pixel, pixels q and q + 2 of a read would meet: 2-way).  The 8-byte stores of a half wave cover two
+//              runs of 128 bytes (2 pixels x 64 B in each channel half): one pass over the 32 banks that writes use each.
+//   LDS      = 4 x 34 x 64 x 6 B + 2 x 32 x 64 x 6 B = 76800 B (dynamic), 240 registers, no spill: two workgroups per CU - measured
+//              against one (conv1_2 4.48 - 4.63 ms against 4.91 - 4.92)
+//   chains   = the bf16 MFMA does not round into its accumulator as an fp32 fma does: one chain over a workgroup's whole share
+//              (25088 pixels at conv1_2, batch 64) ended 2.7e-5 from the fp32 form, and the error grows with the chain and the size
+//              of the running sum.  Every WRS_FLUSH = 32 row steps a wave adds its accumulators to its part of the workgroup's
+//              partial with ordinary fp32 additions (the first time a store) and starts them from zero: 6.1e-6 there
+//   schedule = per row step 18 rounds (2 chunks of 16 pixels x 9 taps) of six MFMAs; the six transposing reads of round i + 1 are
+//              issued in front of the MFMAs of round i, held there by scheduling fences
 #include "hk_common.h"
 #include "hk_partial_sum.h"
 #include "../../include/hawkeye_hip.h"
@@ -188,6 +218,226 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_kernel(const float* __rest
         for (int i = 0; i < 16; ++i) pb[(8 * (i >> 2) + (i & 3)) * (9 * WRW_CI) + t * WRW_CI] = acc[t][i];
 }
 
+// ---- the split form: the same walk on the bf16 matrix pipe (header: "Split form") ----
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int WRS_PIX = 32 * 2;                          // bytes of a pixel in a plane: 32 channels, bf16
+constexpr int WRS_XPLANE = (WRW_SW + 2) * WRS_PIX;       // 2176 B: [34 pixels][32 channels] of one piece, one channel half
+constexpr int WRS_DPLANE = WRW_SW * WRS_PIX;             // 2048 B
+constexpr int WRS_XSLOT = 6 * WRS_XPLANE;                // [piece hi, mid, lo][channel half]: 13056 B
+constexpr int WRS_DBUF = 6 * WRS_DPLANE;                 // 12288 B
+constexpr int WRS_LDS = 4 * WRS_XSLOT + 2 * WRS_DBUF;    // 76800 B: two workgroups per CU in 160 KB
+constexpr int WRS_FLUSH = 32;                            // row steps (1024 pixels) an accumulator chain runs before it is added to the partial
+
+// four bf16 as floats: the packed pairs' own bits (one shift or mask each; a vector conversion here is compiled to a second round of
+// single conversions of the source)
+__device__ __forceinline__ f32x4 wrs_widen(bf16x4 p) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const u32x2 u = __builtin_bit_cast(u32x2, p);
+    const u32x4 w = {u[0] << 16, u[0] & 0xffff0000u, u[1] << 16, u[1] & 0xffff0000u};
+    return __builtin_bit_cast(f32x4, w);
+}
+// a = hi + mid + lo to 2^-27 |a|: round to nearest each time, the two differences are exact in fp32.  0 -> three zeros
+__device__ __forceinline__ void wrs_split(f32x4 v, bf16x4 (&p)[3]) {
+    p[0] = __builtin_convertvector(v, bf16x4);
+    v -= wrs_widen(p[0]);
+    p[1] = __builtin_convertvector(v, bf16x4);
+    v -= wrs_widen(p[1]);
+    p[2] = __builtin_convertvector(v, bf16x4);
+}
+// float4 idx of a row segment (pixel idx / 16, channels 4 (idx % 16) ..+3) -> the three pieces, 8 bytes each, at
+// [piece][channel half = (idx % 16) / 8][pixel][4 (idx % 8)] of the planes at `base` (plane = bytes of one plane)
+__device__ __forceinline__ void wrs_store(char* base, int plane, f32x4 v) {
+    bf16x4 p[3];
+    wrs_split(v, p);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(base + 2 * s * plane) = p[s];
+}
+__device__ __forceinline__ void wrs_store_x(char* xs, int slot, const WrwStage& st, bool rok, const f32x4 (&v)[3]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const int tid = threadIdx.x;
+    char* d = xs + slot * WRS_XSLOT + ((tid >> 3) & 1) * WRS_XPLANE + (tid >> 4) * WRS_PIX + (tid & 7) * 8;
+    wrs_store(d, WRS_XPLANE, (rok && st.xok[0]) ? v[0] : zero);
+    wrs_store(d + 16 * WRS_PIX, WRS_XPLANE, (rok && st.xok[1]) ? v[1] : zero);
+    if (tid + 512 < WRW_XF4) wrs_store(d + 32 * WRS_PIX, WRS_XPLANE, (rok && st.xok[2]) ? v[2] : zero);
+}
+__device__ __forceinline__ void wrs_store_dy(char* ds, int buf, const WrwStage& st, const f32x4 (&v)[2]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const int tid = threadIdx.x;
+    char* d = ds + buf * WRS_DBUF + ((tid >> 3) & 1) * WRS_DPLANE + (tid >> 4) * WRS_PIX + (tid & 7) * 8;
+    wrs_store(d, WRS_DPLANE, st.dok[0] ? v[0] : zero);
+    wrs_store(d + 16 * WRS_PIX, WRS_DPLANE, st.dok[1] ? v[1] : zero);
+}
+// One operand fragment of v_mfma_f32_32x32x16_bf16: the eight pixels blk .. blk + 7 of this lane's channel.  `blk` = the plane's
+// bytes at (first pixel + 8 (lane / 32), channel 16 ((lane / 16) % 2)): the 4 pixel x 16 channel block of the lane's 16-lane group;
+// i = lane % 16.  On the device two transposing reads - lane 4 q + p of a group gives the address of pixel q, channels 4 p ..+3 and
+// gets the four pixels of channel i -, elsewhere the same eight values one by one.
+__device__ __forceinline__ bf16x8 wrs_frag(const char* blk, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) bf16x4* lds_b64;
+    const char* a = blk + (i >> 2) * WRS_PIX + (i & 3) * 8;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)a);
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)(a + 4 * WRS_PIX));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#else
+    bf16x8 f;
+    for (int q = 0; q < 8; ++q) {
+        __bf16 e;
+        __builtin_memcpy(&e, blk + q * WRS_PIX + i * 2, 2);
+        f[q] = e;
+    }
+    return f;
+#endif
+}
+
+// part (+)= acc; acc = 0.  The first time a plain store: the workspace is not zero-filled
+__device__ __forceinline__ void wrs_flush(float* __restrict__ pb, f32x16 (&acc)[9], bool add) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        int o = t * WRW_CI;
+        HK_PIN_LOADED(o);                                // (the addresses are made here: hoisted out of the row loop they are 288 registers;
+        float* q = pb + o;                               //  the pointer itself stays a global one - a flat access makes every LDS wait a full one)
+        f32x16 v = acc[t];
+        if (add) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] += q[(8 * (i >> 2) + (i & 3)) * (9 * WRW_CI)];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            q[(8 * (i >> 2) + (i & 3)) * (9 * WRW_CI)] = v[i];
+            acc[t][i] = 0.f;
+        }
+        __builtin_amdgcn_sched_barrier(0);               // one tap at a time: sixteen loads in flight, not 144
+    }
+}
+
+// As conv3x3_wrw_kernel (same arguments, grid, jobs, ring, borders, result), with dynamic LDS of WRS_LDS bytes
+__global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                float* __restrict__ part, int H, int W, int Cout, int nstrips,
+                                                                int nrb, int rpb, int njobs) {
+    HK_DYN_LDS16(ldsf);
+    char* xs = reinterpret_cast<char*>(ldsf);            // ring of four x row segments: [slot][piece][channel half][34 pixels][32]
+    char* ds = xs + 4 * WRS_XSLOT;                       // two dy row segments: [buf][piece][channel half][32 pixels][32]
+    const int tid = threadIdx.x, lane = tid & 63, hf = lane >> 5, l15 = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int oh = wave >> 1, ch = wave & 1;            // this wave's 32 output channels x 32 input channels, all nine taps
+    const int slice = blockIdx.y;
+    const int jb = (int)((long long)blockIdx.x * njobs / gridDim.x), je = (int)((long long)(blockIdx.x + 1) * njobs / gridDim.x);
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+
+    const int blk = 8 * hf * WRS_PIX + ((lane >> 4) & 1) * 32;      // this lane's group block inside a plane, first pixel 0
+    const int aoff = oh * WRS_DPLANE + blk, boff = ch * WRS_XPLANE + blk;
+    // this wave's part of the workgroup's partial result (C layout of the 32 x 32 MFMA, as in conv3x3_wrw_kernel).  Every
+    // WRS_FLUSH row steps the accumulators are added to it with ordinary fp32 additions and start again from zero (header: "chains")
+    auto mine = [&]() {                                  // (made anew at every flush: not two more registers through the row loop)
+        const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+        return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 5)) * (9 * WRW_CI) + (w & 1) * 32 + (l & 31);
+    };
+    int since = 0;
+    bool stored = false;
+
+    for (int j = jb; j < je; ++j) {
+        const int strip = j % nstrips, jr = j / nstrips;
+        const int rb = jr % nrb;
+        const long long n = jr / nrb;
+        const int c0 = strip * WRW_SW, r0 = rb * rpb;
+        const int nrows = (r0 + rpb < H ? r0 + rpb : H) - r0;
+        const float* xi = x + n * H * W * WRW_CI;
+        const float* dyi = dy + n * H * W * Cout + slice * WRW_OT;
+        WrwStage st;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int idx = tid + 256 * u, col = c0 - 1 + (idx >> 4);
+            st.xok[u] = idx < WRW_XF4 && col >= 0 && col < W;
+            st.xoff[u] = (long long)(col < 0 ? 0 : (col < W ? col : W - 1)) * WRW_CI + 4 * (idx & 15);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int idx = tid + 256 * u, col = c0 + (idx >> 4);
+            st.dok[u] = col < W;
+            st.doff[u] = (long long)(col < W ? col : W - 1) * Cout + 4 * (idx & 15);
+        }
+        f32x4 vx[3], vd[2];
+        wrw_load_dy(dyi, st, r0, H, W, Cout, vd);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, vx);
+            wrw_loads_landed(vx, vd);
+            wrs_store_x(xs, t, st, rok, vx);
+        }
+        wrs_store_dy(ds, 0, st, vd);
+        __syncthreads();
+        for (int k = 0; k < nrows; ++k) {
+            const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, vx);
+            wrw_load_dy(dyi, st, r0 + k + 1, H, W, Cout, vd);
+            const char* A = ds + (k & 1) * WRS_DBUF + aoff;
+            const char* B[3] = {xs + (k & 3) * WRS_XSLOT + boff, xs + ((k + 1) & 3) * WRS_XSLOT + boff, xs + ((k + 2) & 3) * WRS_XSLOT + boff};
+            // 18 rounds of six MFMAs: (16-pixel chunk of the row, tap); the fragments of round i + 1 are read before the MFMAs of round i
+            bf16x8 a[3], b[3];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                a[s] = wrs_frag(A + 2 * s * WRS_DPLANE, l15);
+                b[s] = wrs_frag(B[0] + 2 * s * WRS_XPLANE, l15);
+            }
+#pragma unroll
+            for (int i = 0; i < 18; ++i) {
+                const int t = i % 9, cn = (i + 1) / 9, tn = (i + 1) % 9;
+                bf16x8 an[3], bn[3];
+                if (i + 1 < 18) {
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) {
+                        bn[s] = wrs_frag(B[tn / 3] + 2 * s * WRS_XPLANE + (16 * cn + tn % 3) * WRS_PIX, l15);
+                        if (tn == 0) an[s] = wrs_frag(A + 2 * s * WRS_DPLANE + 16 * cn * WRS_PIX, l15);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);       // (left alone, the scheduler sinks each read to the MFMA that needs it)
+                // the six products of first and second order, small ones first (they meet a running sum either way: the order
+                // costs nothing and matters only in a chain's first steps)
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[t], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (i + 1 < 18) {
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) {
+                        b[s] = bn[s];
+                        if (tn == 0) a[s] = an[s];
+                    }
+                }
+            }
+            wrw_loads_landed(vx, vd);
+            wrs_store_x(xs, (k + 3) & 3, st, rok, vx);
+            wrs_store_dy(ds, (k + 1) & 1, st, vd);
+            __syncthreads();
+            if (++since == WRS_FLUSH) {                  // (no load of the next step is in flight yet; each wave owns its part)
+                wrs_flush(mine(), acc, stored);
+                since = 0;
+                stored = true;
+            }
+        }
+    }
+    if (since > 0 || !stored) wrs_flush(mine(), acc, stored);
+}
+
+// Which calls the split form serves by default (knob wrw_split at -1): the layers where it beat the fp32 form by more than three
+// times the spread of the fp32 form's own repeats (profiles/wrw_split_timing.json), and nothing that was not measured.
+// Two Cout slices: cleared at 3.2 M pixels (conv2_1, batch 64) and at 0.8 M (batch 16).  One slice: cleared at 12.8 M pixels
+// (conv1_2, batch 64), missed at 3.2 M (batch 16: 0.72 ms faster against a bar of 0.75) - the line is drawn half way
+static bool wrw_split_wins(int N, int H, int W, int Cout) {
+    const long long pixels = (long long)N * H * W;
+    return Cout >= 2 * WRW_OT ? pixels >= 16ll * 224 * 224 : pixels >= 32ll * 448 * 448;
+}
+
 // The split of a problem into jobs and workgroups: the row-block height whose heaviest workgroup has the fewest row steps
 // (a block costs its rows + the two rows that prime the ring), the lowest block count among equals
 struct WrwPlan {
@@ -231,8 +481,15 @@ extern "C" int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N,
     WrwPlan pl;
     if (!wrw_plan(N, H, W, Cout / WRW_OT, pl)) return HK_ERR_UNSUPPORTED;
     float* part = (float*)ws;
-    hipLaunchKernelGGL(conv3x3_wrw_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), 0, (hipStream_t)stream, dy, x, part,
-                       H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
+    const int split = tuning().wrw_split;
+    if (split > 0 || (split < 0 && wrw_split_wins(N, H, W, Cout))) {
+        HK_ALLOW_BIG_LDS(conv3x3_wrw_split_kernel, WRS_LDS);
+        hipLaunchKernelGGL(conv3x3_wrw_split_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), WRS_LDS, (hipStream_t)stream,
+                           dy, x, part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
+    } else {
+        hipLaunchKernelGGL(conv3x3_wrw_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), 0, (hipStream_t)stream, dy, x,
+                           part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
+    }
     HK_LAUNCH_CHECK();
     const int nel = Cout * 9 * WRW_CI;
     hipLaunchKernelGGL(partial_sum_kernel<16>, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, pl.nwg, nel, nel,

@@ -58,6 +58,8 @@ struct Tuning {
     int conv_wrw = 1;       // HK_CONV_WRW      weight gradient of the trunk's 64-input-channel 3 x 3 convolutions: 1: hk_conv3x3_wrw where it is the
                             //                  measured winner (functional.conv3x3_wrw_ok), 0: the library's everywhere
     int wrw_wgs = 0;        // HK_WRW_WGS       hk_conv3x3_wrw: workgroups per 64-wide Cout slice, at most (0: two per CU over all slices; up to 512)
+    int wrw_split = -1;     // HK_WRW_SPLIT     hk_conv3x3_wrw: 0: the fp32-MFMA kernel, 1: the three-way split bf16-MFMA kernel wherever the entry point
+                            //                  serves the call, -1: per layer, the measured winner (conv_wrw.hip: wrw_split_wins)
     int peer_form = 0;      // HK_PEER_FORM     hk_peer_loss: 0: automatic - the one-launch LDS-resident form wherever both logit matrices fit one
                             //                  workgroup's LDS (by launch count: NOT yet timed on the device), 1: the three-launch general form,
                             //                  2: the resident form or HK_ERR_UNSUPPORTED

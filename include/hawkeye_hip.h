@@ -66,6 +66,8 @@ const char* hk_version(void);
  *   "conv_wrw"      1 (default): the trunk routes the weight gradient of its 64-input-channel 3 x 3 convolutions to
  *                   hk_conv3x3_wrw where that is the measured winner; 0: the library's weight gradient everywhere
  *   "wrw_wgs"       hk_conv3x3_wrw: workgroups per 64-wide Cout slice, at most (0 = two per CU over all slices; up to 512)
+ *   "wrw_split"     hk_conv3x3_wrw: 0 = the fp32-MFMA kernel, 1 = the three-way split bf16-MFMA kernel wherever the entry point
+ *                   serves the call, -1 (default) = per layer, the measured winner
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
@@ -302,7 +304,14 @@ int hk_conv1_bias_relu_bwd(const float* dy, const uint8_t* mask, const float* x,
  * Cin == 64, Cout % 64 == 0, 16-byte aligned pointers, any N, H, W >= 1; HK_ERR_UNSUPPORTED (nothing launched) otherwise.  Workspace
  * hk_conv3x3_wrw_ws_bytes(Cin, Cout) bytes (per-workgroup partial results, added in a fixed order: no atomics, no zero-fill, the same
  * input gives the same bits).  Nothing outside the two maps is read.  Replaces the library's weight gradient for those layers; the
- * forward and the input gradient stay the library's. */
+ * forward and the input gradient stay the library's.
+ * Two forms behind the one entry point (knob "wrw_split"; same workspace, same contract): the fp32-MFMA kernel, and a kernel that
+ * splits every x and dy value into three bf16 pieces (hi + mid + lo = the value to 2^-27) and runs the six products of first and
+ * second order on the bf16 matrix pipe with fp32 accumulation - within 3.9e-8 sum |x| |dy| of the exact result before accumulation,
+ * the same 1e-6 sum |x| |dy| elementwise bound as the fp32 form after it, and 1.4 x faster at the trunk's shapes; by default the
+ * layers where it was measured faster go to it.  Domain of that bound: finite inputs with |a| < 2^127 that are zero or no smaller
+ * than about 2^-100 (below, the low pieces are bf16 subnormals and may be flushed).  A non-finite input makes every dw element it
+ * touches non-finite in both forms - NaN in the split form where the fp32 form may give +-inf. */
 size_t hk_conv3x3_wrw_ws_bytes(int Cin, int Cout);
 int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
                    hk_stream_t stream);

@@ -1,0 +1,86 @@
+"""hk_conv3x3_wrw stand-alone at the trunk's two 64-input-channel layers (conv1_2: 64 -> 64 at 448 x 448, conv2_1: 64 -> 128 at
+224 x 224), batch 64 and 16, the fp32-MFMA kernel (knob wrw_split 0) against the three-way split bf16-MFMA kernel (1), each at
+two workgroups per CU (knob wrw_wgs 0: 512 workgroups over all Cout slices) and at one (256 over all slices).
+
+Per row: two warm-up calls, then six timed calls, HIP events around the entry point (the main kernel + partial_sum_kernel); the
+six times, their min and max, and TF/s of the useful 2 * pixels * Cout * 576 FLOP at the min.  The routing rule of DESIGN 3.10 is
+applied to the default (two per CU) rows: a layer goes to the split kernel if its slowest repeat is faster than the fp32 kernel's
+fastest by more than three times the fp32 kernel's own min-max spread.  Writes the rows as json.
+
+    python tools/wrw_rows.py [--out profiles/wrw_split_timing.json]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+LAYERS = {'conv1_2': (448, 64), 'conv2_1': (224, 128)}       # side, Cout
+WARMUP, CALLS = 2, 6
+
+
+def timed(HF, x, dy):
+    for _ in range(WARMUP):
+        HF.conv3x3_wrw_raw(x, dy)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(CALLS):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        HF.conv3x3_wrw_raw(x, dy)
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return ms
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        print('wrw_rows needs an MI355X: nothing is measured without one')
+        sys.exit(2)
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    import hawkeye_amd.functional as HF
+    from hawkeye_amd import _lib
+    result = {'device': torch.cuda.get_device_name(0), 'warmup_calls': WARMUP, 'timed_calls': CALLS,
+              'unit': 'milliseconds per call of hk_conv3x3_wrw (HIP events around the entry point)', 'rows': {}, 'routing': {}}
+    gen = torch.Generator(device=dev).manual_seed(29)
+    for name, (side, cout) in LAYERS.items():
+        for batch in (64, 16):
+            x = torch.empty(batch, 64, side, side, device=dev, memory_format=torch.channels_last).normal_(0.0, 1.0, generator=gen)
+            dy = torch.empty(batch, cout, side, side, device=dev, memory_format=torch.channels_last).normal_(0.0, 1.0, generator=gen)
+            HF.conv3x3_wrw_raw(x[:1], dy[:1])                  # (the workspace is allocated outside the timed calls)
+            flop = 2.0 * batch * side * side * cout * 576
+            rows = {}
+            for split in (0, 1):
+                for per_cu, wgs in ((2, 0), (1, 256 // (cout // 64))):
+                    with _lib.tuning(wrw_split=split, wrw_wgs=wgs):
+                        ms = timed(HF, x, dy)
+                    rows[f'split{split}_wg_per_cu{per_cu}'] = {'ms': [round(m, 4) for m in ms], 'min': round(min(ms), 4), 'max': round(max(ms), 4),
+                                                               'tflops_at_min': round(flop / (min(ms) * 1e-3) / 1e12, 1)}
+            with _lib.tuning(wrw_split=0):
+                a = HF.conv3x3_wrw_raw(x, dy).double()
+            with _lib.tuning(wrw_split=1):
+                b = HF.conv3x3_wrw_raw(x, dy).double()
+            rows['rel_difference_split_vs_fp32'] = float((a - b).norm() / a.norm())
+            key = f'{name}_b{batch}'
+            result['rows'][key] = rows
+            f32, spl = rows['split0_wg_per_cu2'], rows['split1_wg_per_cu2']
+            spread = f32['max'] - f32['min']
+            result['routing'][key] = {'fp32_min': f32['min'], 'fp32_spread': round(spread, 4), 'split_max': spl['max'],
+                                      'gain_ms': round(f32['min'] - spl['max'], 4), 'to_split': bool(f32['min'] - spl['max'] > 3 * spread)}
+            del x, dy
+            torch.cuda.empty_cache()
+    text = json.dumps(result, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(text + '\n')
