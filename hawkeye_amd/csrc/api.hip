@@ -22,7 +22,7 @@ const Knob kKnobs[] = {
     {"lin_walk", "HK_LIN_WALK", &Tuning::lin_walk},           {"bwd_fold", "HK_BWD_FOLD", &Tuning::bwd_fold},
     {"fwd_fold", "HK_FWD_FOLD", &Tuning::fwd_fold},             {"conv_wrw", "HK_CONV_WRW", &Tuning::conv_wrw},
     {"wrw_wgs", "HK_WRW_WGS", &Tuning::wrw_wgs},                {"peer_form", "HK_PEER_FORM", &Tuning::peer_form},
-    {"wrw_split", "HK_WRW_SPLIT", &Tuning::wrw_split},
+    {"wrw_split", "HK_WRW_SPLIT", &Tuning::wrw_split},          {"wrw_wide", "HK_WRW_WIDE", &Tuning::wrw_wide},
 };
 Tuning from_env() {
     Tuning t;

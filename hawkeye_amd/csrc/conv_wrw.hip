@@ -1,5 +1,6 @@
-// Weight gradient of the trunk's 3 x 3 convolutions with 64 input channels (model/backbone/vgg.py:24-57: conv1_2, 64 -> 64 at
-// 448 x 448, and conv2_1, 64 -> 128 at 224 x 224; stride 1, padding 1, fp32, channels_last):
+// Weight gradient of the trunk's 3 x 3 convolutions whose input channel count is a multiple of 64 (model/backbone/vgg.py:24-57; stride 1, padding 1, fp32,
+// channels_last).  First the two layers with 64 input channels (conv1_2, 64 -> 64 at 448 x 448, and conv2_1, 64 -> 128 at 224 x 224),
+// which both forms below serve; "Wide" at the end of this header: the ten layers with 128 - 512 input channels, split form only:
 //   dW[o][kh][kw][ci] = sum over pixels of dy[pix][o] x[pix + (kh - 1, kw - 1)][ci]
 // - a GEMM with M = Cout, N = 9 * 64 = 576 and K = N H W pixels (12.8 M at the metric shape).  The library runs these two
 // layers on a 64 x 64 tile with one 32 x 32 MFMA block per wave (an LDS operand fetch for almost every MFMA) and splits K
@@ -53,13 +54,30 @@
 //              partial with ordinary fp32 additions (the first time a store) and starts them from zero: 6.1e-6 there
 //   schedule = per row step 18 rounds (2 chunks of 16 pixels x 9 taps) of six MFMAs; the six transposing reads of round i + 1 are
 //              issued in front of the MFMAs of round i, held there by scheduling fences
+//
+// Wide (conv3x3_wrw_split_kernel<true>, knob wrw_wide): nothing in the method depends on Cin being 64.  With Cin a multiple of 64 a workgroup owns
+// the 64 x 9 x 64 block of dW of one (Cout slice, Cin slice) pair and reads its 64 input channels out of the Cin-wide pixels of x the
+// way dy's 64 channels have always been read out of Cout-wide pixels: a runtime pixel stride and a channel offset of 64 cslice in the
+// image base, the row segment offsets and the loads; LDS layout, operand reads, ring, borders, chains and schedule are untouched (240
+// registers, no spill, two workgroups per CU, as the 64-channel instantiation, whose code is the parent's but for scalar address
+// arithmetic).  The partial result is [workgroup][Cout][9][Cin] - a row pitch of 9 Cin and a tap pitch of Cin at the flush - and
+// partial_sum_kernel runs over Cout 9 Cin elements.
+//   plan     = two workgroups per CU over ALL slices: max(1, 512 / slices) per slice (conv2_2: 4 slices x 128, conv3_2: 16 x 32,
+//              conv4_2 / conv5_x: 64 x 8), which is also what the workspace holds: 75.5 MB whenever slices <= 512
+//   grid     = (workgroups per slice, Cout slices, Cin slices): the workgroups of a slice are next to each other in the dispatch
+//              order, so with a multiple of 8 workgroups per slice every slice of one pixel share lands on the same XCD and its x and dy rows are
+//              in that L2 for the other slices (HBM: each x slab is needed by Cout / 64 slices, each dy slab by Cin / 64).  The other
+//              order (the slices of a pixel share next to each other) was built, measured and dropped: no different
+//              (profiles/wrw_wide_timing.json, rows `split_slices_adjacent`: within the repeats' spread on all twenty rows)
+//   measured = 190 - 217 TF/s stand-alone at batch 64 where the library's fp32 kernels give 125 - 131, 26.8 ms for the ten layers in
+//              the training step against the library's 48.5
 #include "hk_common.h"
 #include "hk_partial_sum.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
 
-constexpr int WRW_CI = 64;                               // input channels
+constexpr int WRW_CI = 64;                               // input channels per workgroup (all of them, or a 64-wide slice of Cin)
 constexpr int WRW_OT = 64;                               // output channels per workgroup
 constexpr int WRW_SW = 32;                               // strip width (pixels per row step)
 constexpr int WRW_XROW = (WRW_SW + 2) * WRW_CI;          // floats of an x row segment (column halo on both sides)
@@ -78,9 +96,10 @@ struct WrwStage {
 // The loads are untracked (HK_LOAD16_ASYNC: they stay where they are written, in front of the step's MFMAs - left to the compiler,
 // they end up behind the MFMAs, next to the LDS stores that use them), unconditional (clamped, in-bounds addresses), and waited for
 // by wrw_loads_landed() behind the MFMAs; the zeros of the borders are put in on the way to LDS
-__device__ __forceinline__ bool wrw_load_x(const float* __restrict__ xi, const WrwStage& st, int r, int H, int W, f32x4 (&v)[3]) {
+// (cin = floats of an x pixel: the 64-channel slice that `xi` starts at is read out of wider pixels, as dy's is)
+__device__ __forceinline__ bool wrw_load_x(const float* __restrict__ xi, const WrwStage& st, int r, int H, int W, int cin, f32x4 (&v)[3]) {
     const bool rok = r >= 0 && r < H;
-    const float* row = xi + (long long)(r < 0 ? 0 : (r < H ? r : H - 1)) * W * WRW_CI;
+    const float* row = xi + (long long)(r < 0 ? 0 : (r < H ? r : H - 1)) * W * cin;
 #pragma unroll
     for (int u = 0; u < 3; ++u) HK_LOAD16_ASYNC(v[u], row + st.xoff[u]);
     return rok;
@@ -161,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_kernel(const float* __rest
         wrw_load_dy(dyi, st, r0, H, W, Cout, vd);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, vx);
+            const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, WRW_CI, vx);
             wrw_loads_landed(vx, vd);
             wrw_store_x(xs, t, st, rok, vx);
         }
@@ -170,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_kernel(const float* __rest
         for (int k = 0; k < nrows; ++k) {                // output row r0 + k: x rows r0 + k - 1 .. + 1 are ring entries k, k + 1, k + 2
             // the next step's new segments: in flight while this step's MFMAs run.  (A job's last step loads and stores them for
             // nothing: ring entry and dy buffer are the ones the next job's first step does not use)
-            const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, vx);
+            const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, WRW_CI, vx);
             wrw_load_dy(dyi, st, r0 + k + 1, H, W, Cout, vd);
             const float* A = ds + (k & 1) * WRW_DYROW + aoff;
             const float* B0 = xs + (k & 3) * WRW_XROW + boff;
@@ -292,38 +311,43 @@ __device__ __forceinline__ bf16x8 wrs_frag(const char* blk, int i) {
 #endif
 }
 
-// part (+)= acc; acc = 0.  The first time a plain store: the workspace is not zero-filled
-__device__ __forceinline__ void wrs_flush(float* __restrict__ pb, f32x16 (&acc)[9], bool add) {
+// part (+)= acc; acc = 0.  The first time a plain store: the workspace is not zero-filled.  cin = floats of a tap in a row of the
+// partial (a row = one output channel: 9 cin floats)
+__device__ __forceinline__ void wrs_flush(float* __restrict__ pb, f32x16 (&acc)[9], bool add, int cin) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-        int o = t * WRW_CI;
+        int o = t * cin;
         HK_PIN_LOADED(o);                                // (the addresses are made here: hoisted out of the row loop they are 288 registers;
         float* q = pb + o;                               //  the pointer itself stays a global one - a flat access makes every LDS wait a full one)
         f32x16 v = acc[t];
         if (add) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] += q[(8 * (i >> 2) + (i & 3)) * (9 * WRW_CI)];
+            for (int i = 0; i < 16; ++i) v[i] += q[(8 * (i >> 2) + (i & 3)) * (9 * cin)];
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            q[(8 * (i >> 2) + (i & 3)) * (9 * WRW_CI)] = v[i];
+            q[(8 * (i >> 2) + (i & 3)) * (9 * cin)] = v[i];
             acc[t][i] = 0.f;
         }
         __builtin_amdgcn_sched_barrier(0);               // one tap at a time: sixteen loads in flight, not 144
     }
 }
 
-// As conv3x3_wrw_kernel (same arguments, grid, jobs, ring, borders, result), with dynamic LDS of WRS_LDS bytes
+// As conv3x3_wrw_kernel (same grid, jobs, ring, borders, result), with dynamic LDS of WRS_LDS bytes.  WIDE: x [N][H][W][Cin] with
+// Cin a multiple of 64; a workgroup owns the 64 x 9 x 64 block (Cout slice blockIdx.y, Cin slice blockIdx.z) of dW and reads its 64
+// input channels out of the Cin-wide pixels, part [gridDim.x][Cout][9][Cin].  Not WIDE: Cin = 64, as it was.
+template <bool WIDE>
 __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                 float* __restrict__ part, int H, int W, int Cout, int nstrips,
-                                                                int nrb, int rpb, int njobs) {
+                                                                int nrb, int rpb, int njobs, int Cin) {
     HK_DYN_LDS16(ldsf);
     char* xs = reinterpret_cast<char*>(ldsf);            // ring of four x row segments: [slot][piece][channel half][34 pixels][32]
     char* ds = xs + 4 * WRS_XSLOT;                       // two dy row segments: [buf][piece][channel half][32 pixels][32]
     const int tid = threadIdx.x, lane = tid & 63, hf = lane >> 5, l15 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int oh = wave >> 1, ch = wave & 1;            // this wave's 32 output channels x 32 input channels, all nine taps
-    const int slice = blockIdx.y;
+    const int cin = WIDE ? Cin : WRW_CI;                 // floats of an x pixel
+    const int slice = blockIdx.y, cslice = WIDE ? blockIdx.z : 0;
     const int jb = (int)((long long)blockIdx.x * njobs / gridDim.x), je = (int)((long long)(blockIdx.x + 1) * njobs / gridDim.x);
 
     f32x16 acc[9];
@@ -338,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
     // WRS_FLUSH row steps the accumulators are added to it with ordinary fp32 additions and start again from zero (header: "chains")
     auto mine = [&]() {                                  // (made anew at every flush: not two more registers through the row loop)
         const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-        return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 5)) * (9 * WRW_CI) + (w & 1) * 32 + (l & 31);
+        return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 5)) * (9 * cin) + cslice * WRW_CI + (w & 1) * 32 + (l & 31);
     };
     int since = 0;
     bool stored = false;
@@ -349,14 +373,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
         const long long n = jr / nrb;
         const int c0 = strip * WRW_SW, r0 = rb * rpb;
         const int nrows = (r0 + rpb < H ? r0 + rpb : H) - r0;
-        const float* xi = x + n * H * W * WRW_CI;
+        const float* xi = x + n * H * W * cin + cslice * WRW_CI;
         const float* dyi = dy + n * H * W * Cout + slice * WRW_OT;
         WrwStage st;
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
             const int idx = tid + 256 * u, col = c0 - 1 + (idx >> 4);
             st.xok[u] = idx < WRW_XF4 && col >= 0 && col < W;
-            st.xoff[u] = (long long)(col < 0 ? 0 : (col < W ? col : W - 1)) * WRW_CI + 4 * (idx & 15);
+            st.xoff[u] = (long long)(col < 0 ? 0 : (col < W ? col : W - 1)) * cin + 4 * (idx & 15);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -368,14 +392,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
         wrw_load_dy(dyi, st, r0, H, W, Cout, vd);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, vx);
+            const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, cin, vx);
             wrw_loads_landed(vx, vd);
             wrs_store_x(xs, t, st, rok, vx);
         }
         wrs_store_dy(ds, 0, st, vd);
         __syncthreads();
         for (int k = 0; k < nrows; ++k) {
-            const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, vx);
+            const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, cin, vx);
             wrw_load_dy(dyi, st, r0 + k + 1, H, W, Cout, vd);
             const char* A = ds + (k & 1) * WRS_DBUF + aoff;
             const char* B[3] = {xs + (k & 3) * WRS_XSLOT + boff, xs + ((k + 1) & 3) * WRS_XSLOT + boff, xs + ((k + 2) & 3) * WRS_XSLOT + boff};
@@ -420,13 +444,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
             wrs_store_dy(ds, (k + 1) & 1, st, vd);
             __syncthreads();
             if (++since == WRS_FLUSH) {                  // (no load of the next step is in flight yet; each wave owns its part)
-                wrs_flush(mine(), acc, stored);
+                wrs_flush(mine(), acc, stored, cin);
                 since = 0;
                 stored = true;
             }
         }
     }
-    if (since > 0 || !stored) wrs_flush(mine(), acc, stored);
+    if (since > 0 || !stored) wrs_flush(mine(), acc, stored, cin);
 }
 
 // Which calls the split form serves by default (knob wrw_split at -1): the layers where it beat the fp32 form by more than three
@@ -443,10 +467,15 @@ static bool wrw_split_wins(int N, int H, int W, int Cout) {
 struct WrwPlan {
     int nstrips, nrb, rpb, njobs, nwg;
 };
-static bool wrw_plan(int N, int H, int W, int slices, WrwPlan& pl) {
+// Workgroups per slice that the workspace of a wide call (Cin > 64; slice = a 64 x 64 block of (Cout, Cin)) has room for: two
+// workgroups per CU over all slices
+static int wrw_wide_wgs(long long slices) { return slices < 512 ? (int)(512 / slices) : 1; }
+
+static bool wrw_plan(int N, int H, int W, int slices, bool wide, WrwPlan& pl) {
     // two workgroups per CU over all slices (two waves per SIMD cover each other's LDS waits: conv1_2 6.54 ms against 6.72 with one)
-    int wgmax = tuning().wrw_wgs > 0 ? tuning().wrw_wgs : (slices <= 8 ? 512 / slices : 64);
-    if (wgmax > WRW_MAX_WG) wgmax = WRW_MAX_WG;
+    const int room = wide ? wrw_wide_wgs(slices) : WRW_MAX_WG;
+    int wgmax = tuning().wrw_wgs > 0 ? tuning().wrw_wgs : (wide ? room : (slices <= 8 ? 512 / slices : 64));
+    if (wgmax > room) wgmax = room;
     const long long nstrips = ((long long)W + WRW_SW - 1) / WRW_SW, base = (long long)N * nstrips;
     long long best = -1;
     for (int cand = 1; cand <= (H / WRW_MIN_ROWS > 1 ? H / WRW_MIN_ROWS : 1); ++cand) {
@@ -469,29 +498,41 @@ static bool wrw_plan(int N, int H, int W, int slices, WrwPlan& pl) {
 using namespace hk;
 
 extern "C" size_t hk_conv3x3_wrw_ws_bytes(int Cin, int Cout) {      // (for any sizes > 0: the workspace check comes before the shape check)
-    return Cin > 0 && Cout > 0 ? (size_t)WRW_MAX_WG * Cout * 9 * Cin * sizeof(float) : 0;
+    if (Cin <= 0 || Cout <= 0) return 0;
+    const size_t one = (size_t)Cout * 9 * Cin * sizeof(float);       // one workgroup's share: a whole dW
+    if (Cin <= WRW_CI) return WRW_MAX_WG * one;
+    return wrw_wide_wgs(((long long)Cin + WRW_CI - 1) / WRW_CI * (((long long)Cout + WRW_OT - 1) / WRW_OT)) * one;
 }
 
 extern "C" int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N, int H, int W, int Cin, int Cout, void* ws,
                               size_t ws_bytes, hk_stream_t stream) {
     if (!dy || !x || !dw || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return HK_ERR_BAD_ARG;
     if (!ws || ws_bytes < hk_conv3x3_wrw_ws_bytes(Cin, Cout)) return HK_ERR_WORKSPACE;
-    if (Cin != WRW_CI || Cout % WRW_OT != 0 || Cout / WRW_OT > 65535 || !aligned16(dy) || !aligned16(x) || !aligned16(dw) || !aligned16(ws))
+    if (Cin % WRW_CI != 0 || Cout % WRW_OT != 0 || Cout / WRW_OT > 65535 || Cin / WRW_CI > 65535 || (long long)Cout * 9 * Cin > 0x7fffffffll ||
+        !aligned16(dy) || !aligned16(x) || !aligned16(dw) || !aligned16(ws))
         return HK_ERR_UNSUPPORTED;
-    WrwPlan pl;
-    if (!wrw_plan(N, H, W, Cout / WRW_OT, pl)) return HK_ERR_UNSUPPORTED;
-    float* part = (float*)ws;
     const int split = tuning().wrw_split;
-    if (split > 0 || (split < 0 && wrw_split_wins(N, H, W, Cout))) {
-        HK_ALLOW_BIG_LDS(conv3x3_wrw_split_kernel, WRS_LDS);
-        hipLaunchKernelGGL(conv3x3_wrw_split_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), WRS_LDS, (hipStream_t)stream,
-                           dy, x, part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
+    const bool wide = Cin > WRW_CI;                      // only the split form reads a 64-channel slice out of wider x pixels
+    if (wide && (split == 0 || tuning().wrw_wide == 0)) return HK_ERR_UNSUPPORTED;
+    const int oslices = Cout / WRW_OT, cslices = Cin / WRW_CI;
+    if ((long long)oslices * cslices > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
+    WrwPlan pl;
+    if (!wrw_plan(N, H, W, oslices * cslices, wide, pl)) return HK_ERR_UNSUPPORTED;
+    float* part = (float*)ws;
+    if (wide) {
+        HK_ALLOW_BIG_LDS(conv3x3_wrw_split_kernel<true>, WRS_LDS);
+        hipLaunchKernelGGL(conv3x3_wrw_split_kernel<true>, dim3((unsigned)pl.nwg, (unsigned)oslices, (unsigned)cslices), dim3(256), WRS_LDS,
+                           (hipStream_t)stream, dy, x, part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs, Cin);
+    } else if (split > 0 || (split < 0 && wrw_split_wins(N, H, W, Cout))) {
+        HK_ALLOW_BIG_LDS(conv3x3_wrw_split_kernel<false>, WRS_LDS);
+        hipLaunchKernelGGL(conv3x3_wrw_split_kernel<false>, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), WRS_LDS,
+                           (hipStream_t)stream, dy, x, part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs, WRW_CI);
     } else {
         hipLaunchKernelGGL(conv3x3_wrw_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), 0, (hipStream_t)stream, dy, x,
                            part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
     }
     HK_LAUNCH_CHECK();
-    const int nel = Cout * 9 * WRW_CI;
+    const int nel = Cout * 9 * Cin;
     hipLaunchKernelGGL(partial_sum_kernel<16>, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, pl.nwg, nel, nel,
                        dw, (float*)nullptr);
     HK_LAUNCH_CHECK();

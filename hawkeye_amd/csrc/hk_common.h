@@ -55,11 +55,13 @@ struct Tuning {
                             //                  (one launch), -1: always GEMM + dot product + bcnn_rank1_fix_kernel
     int sched_b = 0;        // HK_SCHED_B       > 0: work-split heuristics that depend on the batch size behave as if it were this (tests: the
                             //                  large-batch schedules on small inputs); results do not depend on it
-    int conv_wrw = 1;       // HK_CONV_WRW      weight gradient of the trunk's 64-input-channel 3 x 3 convolutions: 1: hk_conv3x3_wrw where it is the
+    int conv_wrw = 1;       // HK_CONV_WRW      weight gradient of the trunk's 3 x 3 convolutions with a multiple of 64 input channels: 1: hk_conv3x3_wrw where it is the
                             //                  measured winner (functional.conv3x3_wrw_ok), 0: the library's everywhere
-    int wrw_wgs = 0;        // HK_WRW_WGS       hk_conv3x3_wrw: workgroups per 64-wide Cout slice, at most (0: two per CU over all slices; up to 512)
+    int wrw_wgs = 0;        // HK_WRW_WGS       hk_conv3x3_wrw: workgroups per 64 x 64 (Cout, Cin) slice, at most (0: two per CU over all slices; up to 512,
+                            //                  with more than 64 input channels up to what the workspace holds)
     int wrw_split = -1;     // HK_WRW_SPLIT     hk_conv3x3_wrw: 0: the fp32-MFMA kernel, 1: the three-way split bf16-MFMA kernel wherever the entry point
                             //                  serves the call, -1: per layer, the measured winner (conv_wrw.hip: wrw_split_wins)
+    int wrw_wide = 1;       // HK_WRW_WIDE      hk_conv3x3_wrw with more than 64 input channels (split form only): 1: served, 0: refused (HK_ERR_UNSUPPORTED)
     int peer_form = 0;      // HK_PEER_FORM     hk_peer_loss: 0: automatic - the one-launch LDS-resident form wherever both logit matrices fit one
                             //                  workgroup's LDS (by launch count: NOT yet timed on the device), 1: the three-launch general form,
                             //                  2: the resident form or HK_ERR_UNSUPPORTED

@@ -1862,17 +1862,42 @@ def _two(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
 
-def conv3x3_wrw_route(cout, n, h, w):
-    """The dispatch rule of hk_conv3x3_wrw, by measurement (DESIGN 3.10: in-step kernel times at batch 64 and 16 against the
-    library's weight gradient of the same layer): every supported layer goes to the kernel unless the `conv_wrw` knob is 0."""
+# The layers with more than 64 input channels whose weight gradient goes to hk_conv3x3_wrw by default: (Cin, Cout, H, W) -> the batch
+# sizes at which the kernel was measured against the library's weight gradient of that layer and won, stand-alone
+# (profiles/wrw_wide_timing.json: slowest repeat faster than the library's fastest by more than three times the library's own
+# spread) AND inside the training step.  Nothing that was not measured is here.
+WRW_WIDE_WINS = {
+    (128, 128, 224, 224): (64, 16),                                                                    # conv2_2 of VGG-16 at 448 x 448
+    (128, 256, 112, 112): (64, 16), (256, 256, 112, 112): (64, 16),                                    # conv3_1, conv3_2 / conv3_3
+    (256, 512, 56, 56): (64, 16), (512, 512, 56, 56): (64, 16),                                        # conv4_1, conv4_2 / conv4_3
+    (512, 512, 28, 28): (64, 16),                                                                      # conv5_1 / conv5_2 / conv5_3
+}
+
+
+def _knob(name):
     import ctypes
-    v = ctypes.c_int(1)
-    check(_lib.load().hk_tuning_get(b'conv_wrw', ctypes.byref(v)), 'hk_tuning_get(conv_wrw)')
-    return v.value != 0
+    v = ctypes.c_int(0)
+    check(_lib.load().hk_tuning_get(name, ctypes.byref(v)), f'hk_tuning_get({name.decode()})')
+    return v.value
+
+
+def conv3x3_wrw_route(cout, n, h, w, cin=64):
+    """The dispatch rule of hk_conv3x3_wrw, by measurement (DESIGN 3.10: in-step kernel times at batch 64 and 16 against the
+    library's weight gradient of the same layer).  64 input channels: every supported layer goes to the kernel.  More: the
+    layers of WRW_WIDE_WINS at their measured batch sizes (knob `wrw_split` at its default -1), every supported layer with
+    `wrw_split` at 1, none with `wrw_split` or `wrw_wide` at 0 (the entry point refuses them then).  None at all with `conv_wrw` at 0."""
+    if _knob(b'conv_wrw') == 0:
+        return False
+    if cin <= 64:
+        return True
+    split = _knob(b'wrw_split')
+    if _knob(b'wrw_wide') == 0 or split == 0:
+        return False
+    return split > 0 or n in WRW_WIDE_WINS.get((cin, cout, h, w), ())
 
 
 def conv3x3_wrw_ok(x, conv):
-    """Whether hk_conv3x3_wrw computes this convolution's weight gradient: Conv2d(64, 64 k, 3, stride 1, padding 1) with a
+    """Whether hk_conv3x3_wrw computes this convolution's weight gradient: Conv2d(Cin, Cout, 3, stride 1, padding 1), Cin and Cout multiples of 64, with a
     channels_last fp32 weight, on an fp32 channels_last HIP map, and the dispatch rule (conv3x3_wrw_route) sends the layer there.
     Anything else keeps the library's weight gradient (model/backbone/vgg.py)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
@@ -1881,16 +1906,18 @@ def conv3x3_wrw_ok(x, conv):
     w = conv.weight
     if not (w.dtype == torch.float32 and w.device == x.device and w.is_contiguous(memory_format=torch.channels_last)):
         return False
-    if not (conv.in_channels == 64 and x.shape[1] == 64 and conv.out_channels > 0 and conv.out_channels % 64 == 0
+    if not (conv.in_channels > 0 and conv.in_channels % 64 == 0 and x.shape[1] == conv.in_channels and conv.out_channels > 0
+            and conv.out_channels % 64 == 0
             and _two(conv.kernel_size) == (3, 3) and _two(conv.stride) == (1, 1) and _two(conv.padding) == (1, 1)
             and _two(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'):
         return False
-    return conv3x3_wrw_route(conv.out_channels, x.shape[0], x.shape[2], x.shape[3])
+    return conv3x3_wrw_route(conv.out_channels, x.shape[0], x.shape[2], x.shape[3], conv.in_channels)
 
 
 def conv3x3_wrw_raw(x, dy):
-    """dW [Cout, 64, 3, 3] (channels_last strides over the kernel's [Cout][3][3][64] buffer, no copy) of conv2d(x, W, padding=1) from
-    the channels_last maps x [N, 64, H, W] and dy [N, Cout, H, W]; raises where hk_conv3x3_wrw does not serve the call."""
+    """dW [Cout, Cin, 3, 3] (channels_last strides over the kernel's [Cout][3][3][Cin] buffer, no copy) of conv2d(x, W, padding=1)
+    from the channels_last maps x [N, Cin, H, W] and dy [N, Cout, H, W], Cin and Cout multiples of 64; raises where hk_conv3x3_wrw
+    does not serve the call."""
     lib = _lib.load()
     _nhwc(x, 'conv3x3_wrw')
     _nhwc(dy, 'conv3x3_wrw')
@@ -1907,9 +1934,10 @@ def conv3x3_wrw_raw(x, dy):
 
 
 class _Conv3x3Wrw(torch.autograd.Function):
-    """conv2d(x, weight, None, stride 1, padding 1) for 64 input channels: the forward and the input gradient are the library's, the
-    weight gradient is hk_conv3x3_wrw's (csrc/conv_wrw.hip) - the library's own for these layers (model/backbone/vgg.py:24-57,
-    `features[2]` and `features[5]`) runs a 64 x 64 tile with split-K atomics behind a zero-fill."""
+    """conv2d(x, weight, None, stride 1, padding 1) for a multiple of 64 input channels: the forward and the input gradient are the library's, the
+    weight gradient is hk_conv3x3_wrw's (csrc/conv_wrw.hip) - the library's own for the two 64-input-channel layers
+    (model/backbone/vgg.py:24-57, `features[2]` and `features[5]`) runs a 64 x 64 tile with split-K atomics behind a zero-fill, and
+    its kernels for the wider layers stay on the fp32 matrix pipe, which the kernel's split bf16 form leaves."""
 
     @staticmethod
     def forward(ctx, x, weight):

@@ -25,7 +25,10 @@ class ConvStack(nn.Sequential):
     instead of one pass per op (hk_bias_relu_*, csrc/trunk.hip: the framework's elementwise kernels around the
     convolutions are 12.5 % of the BCNN training step, and the full-resolution activation in front of a pool is not
     even written).  The convolutions themselves are MIOpen's, but for the first layer (hk_conv1_bias_relu_*) and the weight
-    gradient of the two layers with 64 input channels (hk_conv3x3_wrw, csrc/conv_wrw.hip).  Anything the kernels do not cover - CPU tensors, NCHW
+    gradient of the layers whose input channel count is a multiple of 64 and that functional.conv3x3_wrw_route sends to hk_conv3x3_wrw (csrc/conv_wrw.hip):
+    the two 64-input-channel layers at any size, and the ten wider layers of VGG-16 at the map and batch sizes at which the kernel
+    was measured faster than the library's (a 448 x 448 input at batch 64 or 16: all ten; any other size stays on the library until it
+    is measured).  Anything the kernels do not cover - CPU tensors, NCHW
     memory, odd map sizes, other dtypes, a child with forward hooks - runs the children one by one as nn.Sequential does."""
 
     def forward(self, x):
@@ -46,7 +49,7 @@ class ConvStack(nn.Sequential):
                     i += 2
                     continue
                 if HF.conv3x3_wrw_ok(x, m):
-                    # 64 input channels: the library's forward and input gradient, the weight gradient on hk_conv3x3_wrw
+                    # a multiple of 64 input channels, a routed layer: the library's forward and input gradient, the weight gradient on hk_conv3x3_wrw
                     y = HF.conv3x3_wrw(x, m.weight)
                 else:
                     y = TF.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)

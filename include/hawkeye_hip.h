@@ -63,11 +63,14 @@ const char* hk_version(void);
  *   "lin_walk"      classifier backward: 1 workgroup s walks the 64-feature chunks s, s + S, ..; 0 a contiguous slab per
  *                   workgroup; -1 (default) the measured winner per kernel
  *   "sched_b"       > 0: batch-size dependent work splits behave as if the batch were this (tests)
- *   "conv_wrw"      1 (default): the trunk routes the weight gradient of its 64-input-channel 3 x 3 convolutions to
+ *   "conv_wrw"      1 (default): the trunk routes the weight gradient of its 3 x 3 convolutions with a multiple of 64 input channels to
  *                   hk_conv3x3_wrw where that is the measured winner; 0: the library's weight gradient everywhere
- *   "wrw_wgs"       hk_conv3x3_wrw: workgroups per 64-wide Cout slice, at most (0 = two per CU over all slices; up to 512)
- *   "wrw_split"     hk_conv3x3_wrw: 0 = the fp32-MFMA kernel, 1 = the three-way split bf16-MFMA kernel wherever the entry point
- *                   serves the call, -1 (default) = per layer, the measured winner
+ *   "wrw_wgs"       hk_conv3x3_wrw: workgroups per 64 x 64 slice of (Cout, Cin), at most (0 = two per CU over all slices; up to 512 with
+ *                   64 input channels, up to what the workspace holds - max(1, 512 / slices) - with more)
+ *   "wrw_split"     hk_conv3x3_wrw: 0 = the fp32-MFMA kernel (64 input channels only), 1 = the three-way split bf16-MFMA kernel wherever
+ *                   the entry point serves the call, -1 (default) = per layer, the measured winner
+ *   "wrw_wide"      hk_conv3x3_wrw with more than 64 input channels: 1 (default) = served (by the split form); 0 = refused with
+ *                   HK_ERR_UNSUPPORTED, as before the split form read wider pixels
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
@@ -297,14 +300,18 @@ int hk_conv1_bias_relu_fwd(const float* x, const float* wt, const float* bias, f
                            int Cout, hk_stream_t stream);
 int hk_conv1_bias_relu_bwd(const float* dy, const uint8_t* mask, const float* x, float* dwt, float* dbias, int N, int H, int W, int Cin,
                            int Cout, void* ws, size_t ws_bytes, hk_stream_t stream);
-/* Weight gradient of a 3 x 3 convolution with 64 input channels (stride 1, padding 1, dilation 1, fp32; the trunk's conv1_2 and conv2_1,
- * model/backbone/vgg.py:24-57), on the matrix pipe with the whole 64 x 576 result of a Cout slice in one workgroup's accumulators:
- *   x [N][H][W][64], dy [N][H][W][Cout] (channels_last maps) -> dw [Cout][3][3][64] (a channels_last [Cout, 64, 3, 3] weight),
+/* Weight gradient of a 3 x 3 convolution whose input channel count is a multiple of 64 (stride 1, padding 1, dilation 1, fp32; every 3 x 3 layer of the trunk
+ * but the first, model/backbone/vgg.py:24-57), on the matrix pipe with the whole 64 x 9 x 64 result of a (Cout slice, Cin slice) pair in
+ * one workgroup's accumulators:
+ *   x [N][H][W][Cin], dy [N][H][W][Cout] (channels_last maps) -> dw [Cout][3][3][Cin] (a channels_last [Cout, Cin, 3, 3] weight),
  *   dw[o][kh][kw][c] = sum over n, h, w of dy[n][h][w][o] x[n][h + kh - 1][w + kw - 1][c], zero outside the image.
- * Cin == 64, Cout % 64 == 0, 16-byte aligned pointers, any N, H, W >= 1; HK_ERR_UNSUPPORTED (nothing launched) otherwise.  Workspace
- * hk_conv3x3_wrw_ws_bytes(Cin, Cout) bytes (per-workgroup partial results, added in a fixed order: no atomics, no zero-fill, the same
- * input gives the same bits).  Nothing outside the two maps is read.  Replaces the library's weight gradient for those layers; the
- * forward and the input gradient stay the library's.
+ * Cin % 64 == 0, Cout % 64 == 0, Cout 9 Cin < 2^31, 16-byte aligned pointers, any N, H, W >= 1; HK_ERR_UNSUPPORTED (nothing launched)
+ * otherwise, and for Cin > 64 with the knob "wrw_split" or "wrw_wide" at 0 (only the split form below reads a 64-channel slice out of
+ * wider pixels).  Workspace hk_conv3x3_wrw_ws_bytes(Cin, Cout) bytes - a function of the two widths only: per-workgroup partial
+ * results [workgroup][Cout][9][Cin], 512 of them for Cin = 64, max(1, 512 / slices) for more, 75.5 MB up to 512 slices -, added in
+ * a fixed order: no atomics, no zero-fill, the same input gives the same bits.  Nothing outside the two maps is read.  Replaces the
+ * library's weight gradient for the layers where it was measured faster (functional.conv3x3_wrw_route); the forward and the input
+ * gradient stay the library's.
  * Two forms behind the one entry point (knob "wrw_split"; same workspace, same contract): the fp32-MFMA kernel, and a kernel that
  * splits every x and dy value into three bf16 pieces (hi + mid + lo = the value to 2^-27) and runs the six products of first and
  * second order on the bf16 matrix pipe with fp32 accumulation - within 3.9e-8 sum |x| |dy| of the exact result before accumulation,

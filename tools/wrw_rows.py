@@ -7,7 +7,14 @@ six times, their min and max, and TF/s of the useful 2 * pixels * Cout * 576 FLO
 applied to the default (two per CU) rows: a layer goes to the split kernel if its slowest repeat is faster than the fp32 kernel's
 fastest by more than three times the fp32 kernel's own min-max spread.  Writes the rows as json.
 
-    python tools/wrw_rows.py [--out profiles/wrw_split_timing.json]"""
+    python tools/wrw_rows.py [--out profiles/wrw_split_timing.json]
+
+--set wide: the trunk's ten layers with more than 64 input channels at batch 64 and 16, hk_conv3x3_wrw (the split form on 64-channel
+slices of x) against the library's weight gradient (torch.ops.aten.convolution_backward, mask (False, True, False)), same calls
+and the same bar: a layer is routed if the kernel's slowest repeat is faster than the library's fastest by more than three times
+the library's own min-max spread.  The file is rewritten after every row.
+
+    python tools/wrw_rows.py --set wide [--out profiles/wrw_wide_timing.json]"""
 import argparse
 import json
 import os
@@ -20,37 +27,44 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 LAYERS = {'conv1_2': (448, 64), 'conv2_1': (224, 128)}       # side, Cout
+# side, Cin, Cout at a 448 x 448 input
+WIDE_LAYERS = {'conv2_2': (224, 128, 128), 'conv3_1': (112, 128, 256), 'conv3_2': (112, 256, 256), 'conv3_3': (112, 256, 256),
+               'conv4_1': (56, 256, 512), 'conv4_2': (56, 512, 512), 'conv4_3': (56, 512, 512), 'conv5_1': (28, 512, 512),
+               'conv5_2': (28, 512, 512), 'conv5_3': (28, 512, 512)}
 WARMUP, CALLS = 2, 6
 
 
-def timed(HF, x, dy):
+def timed(HF, x, dy, call=None):
+    call = call or HF.conv3x3_wrw_raw
     for _ in range(WARMUP):
-        HF.conv3x3_wrw_raw(x, dy)
+        call(x, dy)
     torch.cuda.synchronize()
     ms = []
     for _ in range(CALLS):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        HF.conv3x3_wrw_raw(x, dy)
+        call(x, dy)
         t1.record()
         t1.synchronize()
         ms.append(t0.elapsed_time(t1))
     return ms
 
 
-if __name__ == '__main__':
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        print('wrw_rows needs an MI355X: nothing is measured without one')
-        sys.exit(2)
-    dev = torch.device('cuda', 0)
-    torch.cuda.set_device(dev)
-    import hawkeye_amd.functional as HF
-    from hawkeye_amd import _lib
-    result = {'device': torch.cuda.get_device_name(0), 'warmup_calls': WARMUP, 'timed_calls': CALLS,
-              'unit': 'milliseconds per call of hk_conv3x3_wrw (HIP events around the entry point)', 'rows': {}, 'routing': {}}
+def row(ms, flop):
+    return {'ms': [round(m, 4) for m in ms], 'min': round(min(ms), 4), 'max': round(max(ms), 4),
+            'tflops_at_min': round(flop / (min(ms) * 1e-3) / 1e12, 1)}
+
+
+def write(result, out):
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            f.write(json.dumps(result, indent=1) + '\n')
+
+
+def split_rows(HF, _lib, dev, result):
+    """The two 64-input-channel layers: fp32 form against split form, two and one workgroup per CU."""
+    result['unit'] = 'milliseconds per call of hk_conv3x3_wrw (HIP events around the entry point)'
     gen = torch.Generator(device=dev).manual_seed(29)
     for name, (side, cout) in LAYERS.items():
         for batch in (64, 16):
@@ -62,9 +76,7 @@ if __name__ == '__main__':
             for split in (0, 1):
                 for per_cu, wgs in ((2, 0), (1, 256 // (cout // 64))):
                     with _lib.tuning(wrw_split=split, wrw_wgs=wgs):
-                        ms = timed(HF, x, dy)
-                    rows[f'split{split}_wg_per_cu{per_cu}'] = {'ms': [round(m, 4) for m in ms], 'min': round(min(ms), 4), 'max': round(max(ms), 4),
-                                                               'tflops_at_min': round(flop / (min(ms) * 1e-3) / 1e12, 1)}
+                        rows[f'split{split}_wg_per_cu{per_cu}'] = row(timed(HF, x, dy), flop)
             with _lib.tuning(wrw_split=0):
                 a = HF.conv3x3_wrw_raw(x, dy).double()
             with _lib.tuning(wrw_split=1):
@@ -78,9 +90,55 @@ if __name__ == '__main__':
                                       'gain_ms': round(f32['min'] - spl['max'], 4), 'to_split': bool(f32['min'] - spl['max'] > 3 * spread)}
             del x, dy
             torch.cuda.empty_cache()
-    text = json.dumps(result, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(text + '\n')
+
+
+def wide_rows(HF, dev, result, out):
+    """The ten layers with more than 64 input channels: the library's weight gradient against hk_conv3x3_wrw."""
+    from hawkeye_amd.miopen_cache import use_in_tree_cache
+    use_in_tree_cache()                                        # the library's kernels of the training step, not a fresh search
+    result['unit'] = ('milliseconds per call (HIP events): `library` = torch.ops.aten.convolution_backward, weight gradient only '
+                      '(its zero-fill included), `split` = hk_conv3x3_wrw (the main kernel + partial_sum_kernel)')
+    gen = torch.Generator(device=dev).manual_seed(31)
+    for batch in (64, 16):
+        for name, (side, cin, cout) in WIDE_LAYERS.items():
+            x = torch.empty(batch, cin, side, side, device=dev, memory_format=torch.channels_last).normal_(0.0, 1.0, generator=gen)
+            dy = torch.empty(batch, cout, side, side, device=dev, memory_format=torch.channels_last).normal_(0.0, 1.0, generator=gen)
+            wt = torch.empty(cout, cin, 3, 3, device=dev).contiguous(memory_format=torch.channels_last)
+            library = lambda a, b: torch.ops.aten.convolution_backward(b, a, wt, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                                                                        (False, True, False))[1]
+            HF.conv3x3_wrw_raw(x[:1], dy[:1])                  # (the workspace is allocated outside the timed calls)
+            flop = 2.0 * batch * side * side * cout * 9 * cin
+            rows = {'library': row(timed(HF, x, dy, library), flop), 'split': row(timed(HF, x, dy), flop)}
+            a, b = library(x, dy).double(), HF.conv3x3_wrw_raw(x, dy).double()
+            rows['rel_difference_split_vs_library'] = float((a - b).norm() / a.norm())
+            key = f'{name}_b{batch}'
+            result['rows'][key] = rows
+            lib, spl = rows['library'], rows['split']
+            spread = lib['max'] - lib['min']
+            result['routing'][key] = {'library_min': lib['min'], 'library_spread': round(spread, 4), 'split_max': spl['max'],
+                                      'gain_ms': round(lib['min'] - spl['max'], 4), 'to_kernel': bool(lib['min'] - spl['max'] > 3 * spread)}
+            print(key, result['routing'][key], flush=True)
+            write(result, out)                                 # (after every row: a run cut short leaves what it measured)
+            del x, dy, wt, a, b
+            torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--set', default='split', choices=['split', 'wide'])
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        print('wrw_rows needs an MI355X: nothing is measured without one')
+        sys.exit(2)
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    import hawkeye_amd.functional as HF
+    from hawkeye_amd import _lib
+    result = {'device': torch.cuda.get_device_name(0), 'warmup_calls': WARMUP, 'timed_calls': CALLS, 'rows': {}, 'routing': {}}
+    if args.set == 'wide':
+        wide_rows(HF, dev, result, args.out)
+    else:
+        split_rows(HF, _lib, dev, result)
+    print(json.dumps(result, indent=1))
+    write(result, args.out)
