@@ -128,11 +128,18 @@ SIGNATURES = {
     'hk_dcl_swap_law': (c_i, [c_f] * 6 + [c_i] * 5 + [c_f]),
 }
 
+# the trunk's forward and input gradient; mirrors include/hawkeye_conv.h one to one (a table of its own, like the header)
+TRUNK_SIGNATURES = {
+    'hk_conv3x3_ws_bytes': (c_sz, [c_i, c_i]),
+    'hk_conv3x3_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_conv3x3_bwd_data': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
+}
+
 
 def attach(lib):
-    """Give every function of SIGNATURES its prototype on a library object (the gfx950 build, or whatever stands in for
-    it).  Returns the library."""
-    for name, (res, args) in SIGNATURES.items():
+    """Give every function of SIGNATURES and TRUNK_SIGNATURES its prototype on a library object (the gfx950 build, or whatever
+    stands in for it).  Returns the library."""
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args

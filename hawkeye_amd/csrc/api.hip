@@ -23,6 +23,7 @@ const Knob kKnobs[] = {
     {"fwd_fold", "HK_FWD_FOLD", &Tuning::fwd_fold},             {"conv_wrw", "HK_CONV_WRW", &Tuning::conv_wrw},
     {"wrw_wgs", "HK_WRW_WGS", &Tuning::wrw_wgs},                {"peer_form", "HK_PEER_FORM", &Tuning::peer_form},
     {"wrw_split", "HK_WRW_SPLIT", &Tuning::wrw_split},          {"wrw_wide", "HK_WRW_WIDE", &Tuning::wrw_wide},
+    {"conv_fwd", "HK_CONV_FWD", &Tuning::conv_fwd},             {"conv_bwd_data", "HK_CONV_BWD_DATA", &Tuning::conv_bwd_data},
 };
 Tuning from_env() {
     Tuning t;

@@ -1,0 +1,307 @@
+// Forward and input gradient of the trunk's 3 x 3 convolutions whose channel counts are multiples of 64 (model/backbone/vgg.py:24-57;
+// stride 1, padding 1, fp32, channels_last), on the bf16 matrix pipe with the three-way split of conv_wrw.hip ("Split form" there):
+//   y[n][h][w][co] = sum over kh, kw, ci of x[n][h + kh - 1][w + kw - 1][ci] Wt[co][kh][kw][ci]
+// - a GEMM with M = Cout, N = pixels, K = 9 Cin.  The library runs it on the fp32 matrix pipe at 131 - 136 TF/s of a practical 140
+// (DESIGN 3.10); the split form's six bf16 products per fp32 product leave that pipe for one that is 16 x as fast.  The input
+// gradient is the same sum over dy with W'[ci][kh][kw][co] = W[co][2 - kh][2 - kw][ci]: ONE main kernel behind ONE pre-pass
+// kernel, which runs once per call and reads W' out of W when its `transposed` flag is set.
+//
+//   pre-pass = conv3x3_wsplit_kernel splits the weights (hk_split_bf16.h) once per call and writes them in the order the main kernel
+//              stages them: [Cout tile of 64][Cin chunk of 32][tap][piece hi, mid, lo][64 co][40 bf16] - the 32 channels of a row and
+//              8 of padding, the LDS image itself, so that staging is a 16-byte copy per thread and load.  `transposed` reads W'
+//              out of W.  Not cached across calls: the weights change every step
+//   tile     = a workgroup (four waves) owns 64 output channels x 4 rows x 32 columns of one image; wave r owns row r: two 32 x 32
+//              MFMA blocks (co 0 - 31, 32 - 63) x 32 pixels.  The weights are the operand whose index is the accumulator ROW, so a
+//              lane ends with 4 consecutive output channels of one pixel per accumulator quad: 16-byte stores, 128 contiguous
+//              bytes per pixel and block.  Nothing is accumulated in memory: no atomics, no split-K, no zero-fill, same bits each run
+//   K        = the channel axis, contiguous in NHWC x and in [co][tap][ci] weights: a fragment (8 consecutive k of one row) is 16
+//              contiguous bytes of a [pixel][32 channels] bf16 plane - a plain ds_read_b128.  Planes have a pitch of 80 bytes a
+//              pixel (5 l mod 16 is a permutation of the 16-byte slots of a 256-byte bank row: the 16 lanes of a read phase do not meet)
+//   x        = per Cin chunk of 32 the halo tile, 6 rows x 34 columns, is split on its way from registers to LDS (once per element
+//              and workgroup) and used by all nine taps: a tap is an address offset.  Rows and columns outside the image and past a
+//              ragged edge are zeros in LDS; the load itself is made from a clamped, in-bounds address, never skipped
+//   pipeline = the weight tile of a (chunk, tap) is double-buffered (2 x 15360 B): tap t + 1 comes in through registers while the
+//              MFMAs of tap t run; the next chunk's x tile is requested at tap 5 and stored behind tap 8; one barrier per tap
+//              (24 MFMAs per wave), two at a chunk's end
+//   chains   = the bf16 MFMA does not round its running sum as an fp32 fma does (conv_wrw.hip: "chains"): every CF_FLUSH = 3 chunks
+//              (K = 864) the accumulators are added to a second fp32 set with ordinary additions and start again from zero
+//              (one chain of 4608 at Cin = 512, measured on a build without the restart: 2.3 - 8.3e-7 S from float64, inside the 1.5e-6
+//              bound but 2.5 - 4 x the restarted chains' 0.6 - 3.2e-7 and the library's 0.4 - 3.1e-7: DESIGN 3.10)
+//   LDS      = 3 x 16320 + 2 x 15360 = 79680 B (dynamic): two workgroups per CU
+//   grid     = xcd_map over (pixel tile, Cout tile): the Cout tiles of a pixel tile run one after the other on one XCD, so the x
+//              tile comes out of that L2 for all but the first
+//   measured = 175 - 202 TF/s stand-alone at batch 64 where the library's fp32 kernels give 108 - 139; in the training step the twelve
+//              forwards 42.1 ms against 57.5 and the twelve input gradients 40.7 against 59.9, and no zero-fill of an output is left;
+//              matrix pipe 56 - 64 % busy at 1.9 GHz, LDS bank conflicts 7 % of the LDS-active cycles
+#include "hk_common.h"
+#include "hk_split_bf16.h"
+#include "../../include/hawkeye_hip.h"
+
+namespace hk {
+
+constexpr int CF_CO = 64;                                // output channels per workgroup
+constexpr int CF_R = 4;                                  // output rows per workgroup: one per wave
+constexpr int CF_SW = 32;                                // output columns per workgroup
+constexpr int CF_CK = 32;                                // input channels per chunk
+constexpr int CF_PIX = 80;                               // bytes of a pixel (or of a weight row) in a plane: 32 bf16 + 16 bytes
+constexpr int CF_HW = CF_SW + 2;                         // columns of the halo tile
+constexpr int CF_HPIX = (CF_R + 2) * CF_HW;              // 204 pixels
+constexpr int CF_XPLANE = CF_HPIX * CF_PIX;              // 16320 B: one piece of the halo tile
+constexpr int CF_WPLANE = CF_CO * CF_PIX;                // 5120 B: one piece of a (chunk, tap) weight tile
+constexpr int CF_WTAP = 3 * CF_WPLANE;                   // 15360 B
+constexpr int CF_LDS = 3 * CF_XPLANE + 2 * CF_WTAP;      // 79680 B
+constexpr int CF_XF4 = CF_HPIX * (CF_CK / 4);            // 1632 float4 of a halo tile
+constexpr int CF_XU = (CF_XF4 + 255) / 256;              // 7 loads per thread (the last one for 96 threads)
+constexpr int CF_FLUSH = 3;                              // chunks (K = 864) an accumulator chain runs
+
+// w [M][9][K] (transposed: w [K][9][M], read as W'[m][tap][k] = w[k][8 - tap][m]) -> ws [M / 64][K / 32][9][3][64][40] bf16.
+// One thread per four k of a row, padding included (zeros)
+__global__ __launch_bounds__(256) void conv3x3_wsplit_kernel(const float* __restrict__ w, char* __restrict__ ws, int M, int K,
+                                                             int transposed, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int nchunk = K / CF_CK;
+    const int q = (int)(i % 10);
+    long long r = i / 10;
+    const int co = (int)(r % CF_CO);
+    r /= CF_CO;                                          // r = (cot nchunk + chunk) 9 + tap: the tile
+    const int tap = (int)(r % 9);
+    const int chunk = (int)((r / 9) % nchunk), cot = (int)((r / 9) / nchunk);
+    const long long m = (long long)cot * CF_CO + co, k0 = (long long)chunk * CF_CK + 4 * q;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (q < 8) {
+        if (!transposed) {
+            v = *reinterpret_cast<const f32x4*>(w + (m * 9 + tap) * K + k0);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = w[((k0 + e) * 9 + (8 - tap)) * M + m];
+        }
+    }
+    bf16x4 p[3];
+    wrs_split(v, p);
+    char* d = ws + (size_t)r * CF_WTAP + co * CF_PIX + q * 8;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(d + s * CF_WPLANE) = p[s];
+}
+
+// one operand fragment of v_mfma_f32_32x32x16_bf16: 16 contiguous bytes of a plane in LDS
+__device__ __forceinline__ bf16x8 cf_frag(const char* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const __attribute__((address_space(3))) bf16x8*)p;
+#else
+    bf16x8 f;
+    __builtin_memcpy(&f, p, 16);
+    return f;
+#endif
+}
+
+// x [N][H][W][Cin], ws as conv3x3_wsplit_kernel leaves it -> y [N][H][W][Cout].  grid xcd_grid(ntiles, Cout / 64), dynamic LDS CF_LDS.
+// tile = ((n nrb + rb) nstrips + strip): rows [4 rb, 4 rb + 4), columns [32 strip, 32 strip + 32)
+__global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __restrict__ x, const char* __restrict__ ws,
+                                                               float* __restrict__ y, int H, int W, int Cin, int Cout, int nstrips,
+                                                               int nrb, int ntiles) {
+    HK_DYN_LDS16(ldsf);
+    char* xs = reinterpret_cast<char*>(ldsf);            // the halo tile of the chunk: [piece][6 x 34 pixels][80 B]
+    char* wb = xs + 3 * CF_XPLANE;                       // two weight tiles: [buf][piece][64 co][80 B]
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ncot = Cout / CF_CO, nchunk = Cin / CF_CK, total = nchunk * 9;
+    int tile, cot;
+    if (!xcd_map(blockIdx.x, ntiles, ncot, tile, cot)) return;
+    const int strip = tile % nstrips, tr = tile / nstrips;
+    const int rb = tr % nrb;
+    const long long n = tr / nrb;
+    const int c0 = strip * CF_SW, r0 = rb * CF_R;
+    const float* xi = x + n * H * W * Cin;
+    const char* wt = ws + (size_t)cot * total * CF_WTAP + tid * 16;
+
+    // this thread's float4 loads of a halo tile: float4 idx -> pixel idx / 8 (row r0 - 1 + pixel / 34, column c0 - 1 + pixel % 34),
+    // channels 4 (idx % 8) ..+3 of the chunk; clamped into the image, and whether they count
+    long long xoff[CF_XU];
+    unsigned xok = 0;
+#pragma unroll
+    for (int u = 0; u < CF_XU; ++u) {
+        const int idx = tid + 256 * u;
+        const bool in = idx < CF_XF4;
+        const int p = in ? idx >> 3 : 0, hr = p / CF_HW, hc = p - hr * CF_HW;
+        const int row = r0 - 1 + hr, col = c0 - 1 + hc;
+        if (in && row >= 0 && row < H && col >= 0 && col < W) xok |= 1u << u;
+        const int rc = row < 0 ? 0 : (row < H ? row : H - 1), cc = col < 0 ? 0 : (col < W ? col : W - 1);
+        xoff[u] = ((long long)rc * W + cc) * Cin + 4 * (idx & 7);
+    }
+    const int xdst = (tid >> 3) * CF_PIX + (tid & 7) * 8;                      // + 32 u pixels
+    const int w3 = tid < 192 ? 3 * 4096 : 0;                                   // the fourth piece of a weight tile: 3072 B, three waves
+
+    f32x4 vx[CF_XU], vw[4];
+    auto load_x = [&](int chunk) {
+        const float* b = xi + chunk * CF_CK;
+#pragma unroll
+        for (int u = 0; u < CF_XU; ++u) HK_LOAD16_ASYNC(vx[u], b + xoff[u]);
+    };
+    auto load_w = [&](int it) {
+        const char* b = wt + (size_t)it * CF_WTAP;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) HK_LOAD16_ASYNC(vw[u], reinterpret_cast<const float*>(b + 4096 * u));
+        HK_LOAD16_ASYNC(vw[3], reinterpret_cast<const float*>(b + w3));
+    };
+    auto store_x = [&]() {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < CF_XU; ++u) {
+            if (tid + 256 * u < CF_XF4) {
+                bf16x4 p[3];
+                wrs_split(((xok >> u) & 1) ? vx[u] : zero, p);
+#pragma unroll
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(xs + s * CF_XPLANE + xdst + u * 32 * CF_PIX) = p[s];
+            }
+        }
+    };
+    auto store_w = [&](int buf) {
+        char* d = wb + buf * CF_WTAP + tid * 16;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) *reinterpret_cast<f32x4*>(d + 4096 * u) = vw[u];
+        if (tid < 192) *reinterpret_cast<f32x4*>(d + 3 * 4096) = vw[3];
+    };
+
+    f32x16 acc[2], sum[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[cb][i] = sum[cb][i] = 0.f;
+
+    load_w(0);
+    load_x(0);
+    __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) HK_PIN_LOADED(vw[u]);
+#pragma unroll
+    for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
+    store_x();
+    store_w(0);
+    __syncthreads();
+
+    const int aoff = l31 * CF_PIX + hf * 16;                        // this lane's weight row (+ 32 rows for the second block)
+    const int boff = (wave * CF_HW + l31) * CF_PIX + hf * 16;       // this lane's pixel at tap (0, 0)
+    int since = 0;
+    for (int chunk = 0; chunk < nchunk; ++chunk) {
+        const bool more = chunk + 1 < nchunk;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int it = chunk * 9 + tap;
+            // the next weight tile (the last step loads its own again: an unconditional, in-bounds load) and, at tap 5, the next
+            // chunk's x tile: in flight while this tap's MFMAs run
+            load_w(it + 1 < total ? it + 1 : it);
+            if (tap == 5) load_x(more ? chunk + 1 : chunk);
+            const char* A = wb + (it & 1) * CF_WTAP + aoff;
+            const char* B = xs + boff + ((tap / 3) * CF_HW + tap % 3) * CF_PIX;
+            bf16x8 a[2][2][3], b[2][3];
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    b[ks][s] = cf_frag(B + s * CF_XPLANE + ks * 32);
+                    a[ks][0][s] = cf_frag(A + s * CF_WPLANE + ks * 32);
+                    a[ks][1][s] = cf_frag(A + s * CF_WPLANE + 32 * CF_PIX + ks * 32);
+                }
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    // the six products of first and second order, small ones first (conv_wrw.hip)
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][1], b[ks][1], acc[cb], 0, 0, 0);
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][0], b[ks][2], acc[cb], 0, 0, 0);
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][2], b[ks][0], acc[cb], 0, 0, 0);
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][0], b[ks][1], acc[cb], 0, 0, 0);
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][1], b[ks][0], acc[cb], 0, 0, 0);
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][0], b[ks][0], acc[cb], 0, 0, 0);
+                }
+            // the weight loads were issued first: at tap 5 the seven x loads behind them stay in flight until tap 6's wait
+            if (tap == 5) __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(CF_XU));
+            else __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
+#pragma unroll
+            for (int u = 0; u < 4; ++u) HK_PIN_LOADED(vw[u]);
+            if (tap == 6) {
+#pragma unroll
+                for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
+            }
+            store_w((it + 1) & 1);                       // the buffer tap - 1 read: a barrier ago
+            if (tap == 8 && more) {
+                __syncthreads();                         // every wave is past its last read of the chunk's x tile
+                store_x();
+            }
+            __syncthreads();
+        }
+        if (++since == CF_FLUSH) {
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                sum[cb] += acc[cb];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[cb][i] = 0.f;
+            }
+            since = 0;
+        }
+    }
+    // C layout of the 32 x 32 MFMA: column = lane & 31 (pixel), row = 8 (i / 4) + 4 (lane >> 5) + i % 4 (output channel)
+    const int row = r0 + wave, col = c0 + l31;
+    if (row < H && col < W) {
+        float* yp = y + ((n * H + row) * W + col) * Cout + cot * CF_CO + 4 * hf;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = sum[cb][4 * j + e] + acc[cb][4 * j + e];
+                *reinterpret_cast<f32x4*>(yp + cb * 32 + 8 * j) = v;
+            }
+    }
+}
+
+// x [N][H][W][K] (*) w -> y [N][H][W][M]: the pre-pass and the main kernel; M, K multiples of 64
+static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
+                       hipStream_t stream) {
+    const long long nstrips = ((long long)W + CF_SW - 1) / CF_SW, nrb = ((long long)H + CF_R - 1) / CF_R, ntiles = N * nrb * nstrips;
+    const int ncot = M / CF_CO;
+    if ((ntiles + NXCD) * ncot > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
+    const long long total = (long long)ncot * (K / CF_CK) * 9 * CF_CO * 10;
+    hipLaunchKernelGGL(conv3x3_wsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (char*)ws, M, K,
+                       transposed ? 1 : 0, total);
+    HK_LAUNCH_CHECK();
+    HK_ALLOW_BIG_LDS(conv3x3_split_kernel, CF_LDS);
+    hipLaunchKernelGGL(conv3x3_split_kernel, dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), CF_LDS, stream, x, (const char*)ws, y,
+                       H, W, K, M, (int)nstrips, (int)nrb, (int)ntiles);
+    HK_LAUNCH_CHECK();
+    return HK_OK;
+}
+
+static int conv3x3_check(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
+                         int knob) {
+    if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return HK_ERR_BAD_ARG;
+    if (!ws || ws_bytes < hk_conv3x3_ws_bytes(Cin, Cout)) return HK_ERR_WORKSPACE;
+    if (Cin % 64 != 0 || Cout % 64 != 0 || (long long)Cout * 9 * Cin > 0x7fffffffll || !aligned16(x) || !aligned16(w) || !aligned16(y) ||
+        !aligned16(ws) || knob == 0)
+        return HK_ERR_UNSUPPORTED;
+    return HK_OK;
+}
+
+}  // namespace hk
+
+using namespace hk;
+
+extern "C" size_t hk_conv3x3_ws_bytes(int Cin, int Cout) {          // (for any sizes > 0: the workspace check comes before the shape check)
+    if (Cin <= 0 || Cout <= 0) return 0;
+    const size_t a = ((size_t)Cout + 63) / 64 * (((size_t)Cin + 31) / 32), b = ((size_t)Cin + 63) / 64 * (((size_t)Cout + 31) / 32);
+    return (a > b ? a : b) * 9 * CF_WTAP;                            // the split weights, either way round
+}
+
+extern "C" int hk_conv3x3_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
+                              hk_stream_t stream) {
+    const int rc = conv3x3_check(x, w, y, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_fwd);
+    return rc != HK_OK ? rc : conv3x3_run(x, w, y, N, H, W, Cin, Cout, false, ws, (hipStream_t)stream);
+}
+
+extern "C" int hk_conv3x3_bwd_data(const float* dy, const float* w, float* dx, int N, int H, int W, int Cin, int Cout, void* ws,
+                                   size_t ws_bytes, hk_stream_t stream) {
+    const int rc = conv3x3_check(dy, w, dx, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_bwd_data);
+    return rc != HK_OK ? rc : conv3x3_run(dy, w, dx, N, H, W, Cout, Cin, true, ws, (hipStream_t)stream);
+}

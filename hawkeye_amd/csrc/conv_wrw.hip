@@ -73,6 +73,7 @@
 //              the training step against the library's 48.5
 #include "hk_common.h"
 #include "hk_partial_sum.h"
+#include "hk_split_bf16.h"
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -238,9 +239,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_kernel(const float* __rest
 }
 
 // ---- the split form: the same walk on the bf16 matrix pipe (header: "Split form") ----
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
+// (the split itself - wrs_split, wrs_widen, the bf16 vector types - is hk_split_bf16.h's: conv_fwd.hip uses it too)
 constexpr int WRS_PIX = 32 * 2;                          // bytes of a pixel in a plane: 32 channels, bf16
 constexpr int WRS_XPLANE = (WRW_SW + 2) * WRS_PIX;       // 2176 B: [34 pixels][32 channels] of one piece, one channel half
 constexpr int WRS_DPLANE = WRW_SW * WRS_PIX;             // 2048 B
@@ -249,23 +248,6 @@ constexpr int WRS_DBUF = 6 * WRS_DPLANE;                 // 12288 B
 constexpr int WRS_LDS = 4 * WRS_XSLOT + 2 * WRS_DBUF;    // 76800 B: two workgroups per CU in 160 KB
 constexpr int WRS_FLUSH = 32;                            // row steps (1024 pixels) an accumulator chain runs before it is added to the partial
 
-// four bf16 as floats: the packed pairs' own bits (one shift or mask each; a vector conversion here is compiled to a second round of
-// single conversions of the source)
-__device__ __forceinline__ f32x4 wrs_widen(bf16x4 p) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x2 u = __builtin_bit_cast(u32x2, p);
-    const u32x4 w = {u[0] << 16, u[0] & 0xffff0000u, u[1] << 16, u[1] & 0xffff0000u};
-    return __builtin_bit_cast(f32x4, w);
-}
-// a = hi + mid + lo to 2^-27 |a|: round to nearest each time, the two differences are exact in fp32.  0 -> three zeros
-__device__ __forceinline__ void wrs_split(f32x4 v, bf16x4 (&p)[3]) {
-    p[0] = __builtin_convertvector(v, bf16x4);
-    v -= wrs_widen(p[0]);
-    p[1] = __builtin_convertvector(v, bf16x4);
-    v -= wrs_widen(p[1]);
-    p[2] = __builtin_convertvector(v, bf16x4);
-}
 // float4 idx of a row segment (pixel idx / 16, channels 4 (idx % 16) ..+3) -> the three pieces, 8 bytes each, at
 // [piece][channel half = (idx % 16) / 8][pixel][4 (idx % 8)] of the planes at `base` (plane = bytes of one plane)
 __device__ __forceinline__ void wrs_store(char* base, int plane, f32x4 v) {

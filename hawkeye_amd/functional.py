@@ -1896,22 +1896,27 @@ def conv3x3_wrw_route(cout, n, h, w, cin=64):
     return split > 0 or n in WRW_WIDE_WINS.get((cin, cout, h, w), ())
 
 
-def conv3x3_wrw_ok(x, conv):
-    """Whether hk_conv3x3_wrw computes this convolution's weight gradient: Conv2d(Cin, Cout, 3, stride 1, padding 1), Cin and Cout multiples of 64, with a
-    channels_last fp32 weight, on an fp32 channels_last HIP map, and the dispatch rule (conv3x3_wrw_route) sends the layer there.
-    Anything else keeps the library's weight gradient (model/backbone/vgg.py)."""
+def _conv3x3_served(x, conv):
+    """What all three trunk kernels (hk_conv3x3_wrw, hk_conv3x3_fwd, hk_conv3x3_bwd_data) ask of a layer and its input, their
+    dispatch rules aside: Conv2d(Cin, Cout, 3, stride 1, padding 1), Cin and Cout multiples of 64, zeros padding, with a
+    channels_last fp32 weight, on a 16-byte aligned fp32 channels_last HIP map."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
             and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
         return False
     w = conv.weight
     if not (w.dtype == torch.float32 and w.device == x.device and w.is_contiguous(memory_format=torch.channels_last)):
         return False
-    if not (conv.in_channels > 0 and conv.in_channels % 64 == 0 and x.shape[1] == conv.in_channels and conv.out_channels > 0
+    return (conv.in_channels > 0 and conv.in_channels % 64 == 0 and x.shape[1] == conv.in_channels and conv.out_channels > 0
             and conv.out_channels % 64 == 0
             and _two(conv.kernel_size) == (3, 3) and _two(conv.stride) == (1, 1) and _two(conv.padding) == (1, 1)
-            and _two(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'):
-        return False
-    return conv3x3_wrw_route(conv.out_channels, x.shape[0], x.shape[2], x.shape[3], conv.in_channels)
+            and _two(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros')
+
+
+def conv3x3_wrw_ok(x, conv):
+    """Whether hk_conv3x3_wrw computes this convolution's weight gradient: the layer and its input are what the trunk kernels serve
+    (_conv3x3_served) and the dispatch rule (conv3x3_wrw_route) sends the layer there.  Anything else keeps the library's weight
+    gradient (model/backbone/vgg.py)."""
+    return _conv3x3_served(x, conv) and conv3x3_wrw_route(conv.out_channels, x.shape[0], x.shape[2], x.shape[3], conv.in_channels)
 
 
 def conv3x3_wrw_raw(x, dy):
@@ -1933,35 +1938,128 @@ def conv3x3_wrw_raw(x, dy):
     return buf.permute(0, 3, 1, 2)
 
 
-class _Conv3x3Wrw(torch.autograd.Function):
-    """conv2d(x, weight, None, stride 1, padding 1) for a multiple of 64 input channels: the forward and the input gradient are the library's, the
-    weight gradient is hk_conv3x3_wrw's (csrc/conv_wrw.hip) - the library's own for the two 64-input-channel layers
-    (model/backbone/vgg.py:24-57, `features[2]` and `features[5]`) runs a 64 x 64 tile with split-K atomics behind a zero-fill, and
-    its kernels for the wider layers stay on the fp32 matrix pipe, which the kernel's split bf16 form leaves."""
+# The layers whose forward goes to hk_conv3x3_fwd, and whose input gradient goes to hk_conv3x3_bwd_data, by default (knobs `conv_fwd` /
+# `conv_bwd_data` at -1): (Cin, Cout, H, W) -> the batch sizes at which the kernel was measured against the library's kernel of that
+# layer and direction and won, stand-alone (profiles/conv_split_timing.json: slowest repeat faster than the library's fastest by more
+# than three times the library's own spread) AND inside the training step.  Nothing that was not measured is here.
+CONV_FWD_WINS = {
+    (64, 64, 448, 448): (64, 16), (64, 128, 224, 224): (64, 16), (128, 128, 224, 224): (64, 16),       # conv1_2, conv2_1, conv2_2 of VGG-16 at 448 x 448
+    (128, 256, 112, 112): (64, 16), (256, 256, 112, 112): (64, 16),                                    # conv3_1, conv3_2 / conv3_3
+    (256, 512, 56, 56): (64, 16), (512, 512, 56, 56): (64, 16),                                        # conv4_1, conv4_2 / conv4_3
+    (512, 512, 28, 28): (64, 16),                                                                      # conv5_1 / conv5_2 / conv5_3
+}
+CONV_BWD_DATA_WINS = {
+    (64, 64, 448, 448): (64, 16), (64, 128, 224, 224): (64, 16), (128, 128, 224, 224): (64, 16),       # conv1_2, conv2_1, conv2_2 of VGG-16 at 448 x 448
+    (128, 256, 112, 112): (64, 16), (256, 256, 112, 112): (64, 16),                                    # conv3_1, conv3_2 / conv3_3
+    (256, 512, 56, 56): (64, 16), (512, 512, 56, 56): (64, 16),                                        # conv4_1, conv4_2 / conv4_3
+    (512, 512, 28, 28): (64, 16),                                                                      # conv5_1 / conv5_2 / conv5_3
+}
+
+
+def _conv3x3_route(knob, table, cin, cout, n, h, w):
+    v = _knob(knob)
+    if v == 0:
+        return False
+    return v > 0 or n in table.get((cin, cout, h, w), ())
+
+
+def conv3x3_fwd_route(cin, cout, n, h, w):
+    """The dispatch rule of hk_conv3x3_fwd: knob `conv_fwd` at -1 (default) the layers of CONV_FWD_WINS at their measured batch
+    sizes, at 0 none, at 1 every layer the entry point serves."""
+    return _conv3x3_route(b'conv_fwd', CONV_FWD_WINS, cin, cout, n, h, w)
+
+
+def conv3x3_bwd_data_route(cin, cout, n, h, w):
+    """The dispatch rule of hk_conv3x3_bwd_data: as conv3x3_fwd_route, with the knob `conv_bwd_data` and CONV_BWD_DATA_WINS."""
+    return _conv3x3_route(b'conv_bwd_data', CONV_BWD_DATA_WINS, cin, cout, n, h, w)
+
+
+def conv3x3_fwd_ok(x, conv):
+    """Whether hk_conv3x3_fwd computes this convolution (conditions as conv3x3_wrw_ok) and conv3x3_fwd_route sends the layer there."""
+    return (_conv3x3_served(x, conv) and conv.weight.data_ptr() % 16 == 0          # (these two kernels read the weight itself)
+            and conv3x3_fwd_route(conv.in_channels, conv.out_channels, x.shape[0], x.shape[2], x.shape[3]))
+
+
+def conv3x3_bwd_data_ok(x, conv):
+    """Whether hk_conv3x3_bwd_data computes this convolution's input gradient and conv3x3_bwd_data_route sends the layer there."""
+    return (_conv3x3_served(x, conv) and conv.weight.data_ptr() % 16 == 0
+            and conv3x3_bwd_data_route(conv.in_channels, conv.out_channels, x.shape[0], x.shape[2], x.shape[3]))
+
+
+def _conv3x3_call(fn, what, src, weight, cout_of_result):
+    lib = _lib.load()
+    _nhwc(src, what)
+    if (weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_contiguous(memory_format=torch.channels_last)
+            or weight.dtype != torch.float32 or weight.device != src.device):
+        raise _lib.HawkeyeHipError(f'{what}: wants a channels_last fp32 [Cout, Cin, 3, 3] weight on {src.device}, got {weight.dtype} {tuple(weight.shape)}')
+    n, _, h, w = src.shape
+    cout, cin = weight.shape[0], weight.shape[1]
+    if src.numel() == 0 or src.shape[1] != (cin if cout_of_result else cout):
+        raise _lib.HawkeyeHipError(f'{what}: map {tuple(src.shape)} does not match the weight {tuple(weight.shape)}')
+    psrc, pw = ptr(src), ptr(weight)                # (a CPU tensor is refused here, before anything is allocated)
+    # (a channels_last tensor of its own, not a permuted view: the trunk's epilogue works in place on it)
+    out = torch.empty((n, cout if cout_of_result else cin, h, w), dtype=torch.float32, device=src.device, memory_format=torch.channels_last)
+    nws = lib.hk_conv3x3_ws_bytes(cin, cout)
+    ws = _ws(nws, src.device)
+    check(getattr(lib, fn)(psrc, pw, ptr(out), n, h, w, cin, cout, ptr(ws), nws, stream()), fn)
+    return out
+
+
+def conv3x3_fwd_raw(x, weight):
+    """conv2d(x, weight, None, stride 1, padding 1) on hk_conv3x3_fwd (csrc/conv_fwd.hip): channels_last x [N, Cin, H, W] and weight
+    [Cout, Cin, 3, 3] -> a new channels_last [N, Cout, H, W]; raises where the entry point does not serve the call."""
+    return _conv3x3_call('hk_conv3x3_fwd', 'conv3x3_fwd', x, weight, True)
+
+
+def conv3x3_bwd_data_raw(dy, weight):
+    """The input gradient of that convolution on hk_conv3x3_bwd_data: channels_last dy [N, Cout, H, W] and the forward's weight ->
+    a new channels_last [N, Cin, H, W]."""
+    return _conv3x3_call('hk_conv3x3_bwd_data', 'conv3x3_bwd_data', dy, weight, False)
+
+
+class _Conv3x3(torch.autograd.Function):
+    """conv2d(x, weight, None, stride 1, padding 1) for multiples of 64 channels, each of its three GEMMs on the project's kernel or the
+    library's, independently: the forward on hk_conv3x3_fwd (`fwd`) or F.conv2d, the input gradient on hk_conv3x3_bwd_data (`bwd`)
+    or aten.convolution_backward, the weight gradient on hk_conv3x3_wrw (`wrw`; csrc/conv_wrw.hip) or aten.convolution_backward.
+    The library's fp32 kernels stay on the fp32 matrix pipe, which the kernels' split bf16 form leaves (model/backbone/vgg.py:24-57)."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, fwd, bwd, wrw):
         ctx.save_for_backward(x, weight)
+        ctx.routes = (bwd, wrw)
+        if fwd:
+            return conv3x3_fwd_raw(x, weight)
         return torch.nn.functional.conv2d(x, weight, None, 1, 1, 1, 1)
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
+        bwd, wrw = ctx.routes
         if dy.dtype != torch.float32:
-            raise _lib.HawkeyeHipError(f'conv3x3_wrw backward: fp32 only, got {dy.dtype}')
+            raise _lib.HawkeyeHipError(f'conv3x3 backward: fp32 only, got {dy.dtype}')
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.ops.aten.convolution_backward(dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
-                                                     (True, False, False))[0]
-        if ctx.needs_input_grad[1]:
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if need_dx and bwd:
+            dx = conv3x3_bwd_data_raw(dy, weight)
+        if need_dw and wrw:
             dw = conv3x3_wrw_raw(x, dy)
-        return dx, dw
+        mask = (need_dx and not bwd, need_dw and not wrw, False)
+        if mask[0] or mask[1]:
+            g = torch.ops.aten.convolution_backward(dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, mask)
+            dx = g[0] if mask[0] else dx
+            dw = g[1] if mask[1] else dw
+        return dx, dw, None, None, None
+
+
+def conv3x3(x, weight, fwd=False, bwd=False, wrw=True):
+    """conv2d(x, weight, None, stride=1, padding=1) with the chosen GEMMs on the project's kernels; see _Conv3x3."""
+    return _Conv3x3.apply(x, weight, bool(fwd), bool(bwd), bool(wrw))
 
 
 def conv3x3_wrw(x, weight):
-    """conv2d(x, weight, None, stride=1, padding=1) with the weight gradient on hk_conv3x3_wrw; see _Conv3x3Wrw."""
-    return _Conv3x3Wrw.apply(x, weight)
+    """conv2d(x, weight, None, stride=1, padding=1) with the weight gradient on hk_conv3x3_wrw; see _Conv3x3."""
+    return _Conv3x3.apply(x, weight, False, False, True)
 
 
 def bias_relu(x, bias):

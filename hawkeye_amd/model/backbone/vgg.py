@@ -24,7 +24,9 @@ class ConvStack(nn.Sequential):
     convolution the bias add, the ReLU and, at the end of a stage, the 2 x 2 max-pool are one pass over the activation
     instead of one pass per op (hk_bias_relu_*, csrc/trunk.hip: the framework's elementwise kernels around the
     convolutions are 12.5 % of the BCNN training step, and the full-resolution activation in front of a pool is not
-    even written).  The convolutions themselves are MIOpen's, but for the first layer (hk_conv1_bias_relu_*) and the weight
+    even written).  The convolutions themselves are MIOpen's, but for the first layer (hk_conv1_bias_relu_*), the forward and the
+    input gradient of the layers that functional.CONV_FWD_WINS / CONV_BWD_DATA_WINS list (hk_conv3x3_fwd / hk_conv3x3_bwd_data,
+    csrc/conv_fwd.hip: the layers and batch sizes at which they were measured faster than the library's), and the weight
     gradient of the layers whose input channel count is a multiple of 64 and that functional.conv3x3_wrw_route sends to hk_conv3x3_wrw (csrc/conv_wrw.hip):
     the two 64-input-channel layers at any size, and the ten wider layers of VGG-16 at the map and batch sizes at which the kernel
     was measured faster than the library's (a 448 x 448 input at batch 64 or 16: all ten; any other size stays on the library until it
@@ -48,9 +50,11 @@ class ConvStack(nn.Sequential):
                     x = HF.conv1_bias_relu(x, m.weight, m.bias)
                     i += 2
                     continue
-                if HF.conv3x3_wrw_ok(x, m):
-                    # a multiple of 64 input channels, a routed layer: the library's forward and input gradient, the weight gradient on hk_conv3x3_wrw
-                    y = HF.conv3x3_wrw(x, m.weight)
+                fwd, bwd, wrw = HF.conv3x3_fwd_ok(x, m), HF.conv3x3_bwd_data_ok(x, m), HF.conv3x3_wrw_ok(x, m)
+                if fwd or bwd or wrw:
+                    # a multiple of 64 channels, a routed layer: each of the three GEMMs on its own kernel where it was measured faster
+                    # (hk_conv3x3_fwd, hk_conv3x3_bwd_data, hk_conv3x3_wrw), the library's otherwise
+                    y = HF.conv3x3(x, m.weight, fwd, bwd, wrw)
                 else:
                     y = TF.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
                 pool = i + 2 < len(mods) and _plain_pool(mods[i + 2])

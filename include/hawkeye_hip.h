@@ -71,6 +71,10 @@ const char* hk_version(void);
  *                   the entry point serves the call, -1 (default) = per layer, the measured winner
  *   "wrw_wide"      hk_conv3x3_wrw with more than 64 input channels: 1 (default) = served (by the split form); 0 = refused with
  *                   HK_ERR_UNSUPPORTED, as before the split form read wider pixels
+ *   "conv_fwd"      forward of the trunk's 3 x 3 convolutions with multiples of 64 channels (hawkeye_conv.h): -1 (default) = the split
+ *                   bf16-MFMA kernel for the layers of the measured table, 0 = the library's everywhere (the entry point then refuses
+ *                   with HK_ERR_UNSUPPORTED), 1 = the kernel wherever the entry point serves the call (tests)
+ *   "conv_bwd_data" the same for the input gradient of those convolutions
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
@@ -660,5 +664,7 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 #ifdef __cplusplus
 }
 #endif
+
+#include "hawkeye_conv.h" /* the trunk's forward and input gradient */
 
 #endif /* HAWKEYE_HIP_H */
