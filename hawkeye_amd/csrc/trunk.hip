@@ -6,18 +6,20 @@
 // These kernels make it ONE pass per convolution and direction, on the channels_last tensors the trunk runs in:
 //
 //   bias_relu_fwd        y = max(x + b, 0) in place on the convolution's output                  (read 1, write 1; was 2 + 2)
-//   bias_relu_bwd        dx = dy where y > 0, db = sum dx                                        (read 2 - or 1 1/16 with the forward's
+//   bias_relu_bwd        dx = 0 where y <= 0, else dy; db = sum dx                               (read 2 - or 1 1/16 with the forward's
 //                        sign mask -, write 1; was 3 + 1 + 1)
 //   bias_relu_pool_fwd   p = maxpool2x2(max(x + b, 0)) + a 2-bit argmax per element              (read 1, write 1/4 + 1/64;
 //                        the full-resolution activation is never written: nobody needs it - the next convolution reads p,
 //                        this convolution's weight gradient reads its INPUT - was 2 + 2 + 1.75)
-//   bias_relu_pool_bwd   dx = dp at the argmax where p > 0, else 0; db = sum dx                  (read 1/2 + 1/64, write 1; was 5.75)
+//   bias_relu_pool_bwd   dx = dp at the argmax unless p <= 0, else 0; db = sum dx                (read 1/2 + 1/64, write 1; was 5.75)
 //
 // All HBM-bound streams (16-byte accesses, NHWC: a pixel's channels are contiguous).  Same arithmetic as the ops they
 // replace: x + b then max(., 0) (torch.relu's clamp_min, NaN kept); the pooling window scanned row-major with "strictly
 // greater or NaN replaces" (ATen's max_pool2d: the FIRST maximum wins); the backward routes dp to that element and
-// applies ReLU's mask (y > 0  <=>  p > 0 at the argmax).  db is summed in a fixed order (per thread over its rows, threads of
-// a column quad in order, workgroups in order): deterministic, no atomics.
+// applies ReLU's mask, read off p (the argmax element of y IS p, NaN included).  The mask is ATen's threshold_backward,
+// "y <= 0 -> 0", spelled !(y <= 0) in every kernel here and in the sign bits: a NaN output PASSES its gradient, as it does
+// there.  db is summed in a fixed order (per thread over its rows, threads of a column quad in order, workgroups in order):
+// deterministic, no atomics.
 #include "hk_common.h"
 #include "hk_partial_sum.h"
 #include "../../include/hawkeye_hip.h"
@@ -34,7 +36,7 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v) {
 }
 
 // x [M][C] (M = N H W pixels), C % 4 == 0: in place.  n4 = M C / 4 float4, c4 = C / 4.
-// MASK: also write one byte per float4 - bit t set where channel t of the quad came out positive - so that the backward reads
+// MASK: also write one byte per float4 - bit t set where channel t of the quad came out positive or NaN - so that the backward reads
 // 1/16 of a map instead of the map (the activation itself stays: it is the next convolution's input)
 template <bool MASK>
 __global__ __launch_bounds__(256) void bias_relu_fwd_kernel(float* __restrict__ x, const float* __restrict__ b,
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void bias_relu_fwd_kernel(float* __restrict__ 
             if (j < n4) {
                 const f32x4 r = relu4(v[u] + b4[(int)(j % c4)]);
                 x4[j] = r;
-                if (MASK) mask[j] = (uint8_t)((r[0] > 0.f ? 1 : 0) | (r[1] > 0.f ? 2 : 0) | (r[2] > 0.f ? 4 : 0) | (r[3] > 0.f ? 8 : 0));
+                if (MASK) mask[j] = (uint8_t)((!(r[0] <= 0.f) ? 1 : 0) | (!(r[1] <= 0.f) ? 2 : 0) | (!(r[2] <= 0.f) ? 4 : 0) | (!(r[3] <= 0.f) ? 8 : 0));
             }
         }
     }
@@ -73,7 +75,7 @@ __device__ __forceinline__ void trunk_db_partial(f32x4 acc, float* __restrict__ 
     }
 }
 
-// dx = dy * (y > 0) ; part[block][C] = this workgroup's column sums of dx.  rows = M, workgroup b owns rows
+// dx = dy * !(y <= 0) ; part[block][C] = this workgroup's column sums of dx.  rows = M, workgroup b owns rows
 // [b rpb, (b + 1) rpb).  dx may alias dy.
 template <bool MASK>
 __global__ __launch_bounds__(256) void bias_relu_bwd_kernel(const float* dy, const float* __restrict__ y,
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void bias_relu_bwd_kernel(const float* dy, con
                 f32x4 d;
 #pragma unroll
                 for (int t = 0; t < 4; ++t)                                            // threshold_backward: y <= 0 -> 0
-                    d[t] = (MASK ? ((mk[u] >> t) & 1u) != 0u : v[u][t] > 0.f) ? g[u][t] : 0.f;
+                    d[t] = (MASK ? ((mk[u] >> t) & 1u) != 0u : !(v[u][t] <= 0.f)) ? g[u][t] : 0.f;
                 dx4[rr * c4 + q] = d;
                 acc += d;
             }
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(256) void bias_relu_pool_bwd_kernel(const float* __
             const long long base = ((n * 2 * Ho + 2 * ho) * W + 2 * wo) * c4 + q;
             f32x4 d;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) d[t] = v[u][t] > 0.f ? g[u][t] : 0.f;
+            for (int t = 0; t < 4; ++t) d[t] = !(v[u][t] <= 0.f) ? g[u][t] : 0.f;
             acc += d;
             f32x4 o[4];
 #pragma unroll
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(256) void add_relu_fwd_kernel(float* __restrict__ a
     }
 }
 
-// g = dy where y > 0 else 0 (the gradient of BOTH operands of add_relu)
+// g = 0 where y <= 0 else dy (the gradient of BOTH operands of add_relu)
 __global__ __launch_bounds__(256) void relu_mask_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                             float* __restrict__ g, long long n4) {
     const f32x4* d4 = reinterpret_cast<const f32x4*>(dy);
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(256) void relu_mask_bwd_kernel(const float* __restr
             if (i + k * stride < n4) {
                 f32x4 r;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) r[t] = v[k][t] > 0.f ? u[k][t] : 0.f;
+                for (int t = 0; t < 4; ++t) r[t] = !(v[k][t] <= 0.f) ? u[k][t] : 0.f;
                 g4[i + k * stride] = r;
             }
     }
@@ -438,7 +440,7 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
         const f32x4 v = *reinterpret_cast<const f32x4*>(&T[pl][4 * q]);
         if (pw + pl < npix) {
             reinterpret_cast<f32x4*>(y)[(pw + pl) * 16 + q] = v;
-            if (mask) mask[(pw + pl) * 16 + q] = (uint8_t)((v[0] > 0.f ? 1 : 0) | (v[1] > 0.f ? 2 : 0) | (v[2] > 0.f ? 4 : 0) | (v[3] > 0.f ? 8 : 0));
+            if (mask) mask[(pw + pl) * 16 + q] = (uint8_t)((!(v[0] <= 0.f) ? 1 : 0) | (!(v[1] <= 0.f) ? 2 : 0) | (!(v[2] <= 0.f) ? 4 : 0) | (!(v[3] <= 0.f) ? 8 : 0));
         }
     }
 }

@@ -211,6 +211,125 @@ def test_bias_relu_backward_from_the_sign_mask_equals_the_one_from_the_map(F):
     assert torch.equal(res[0][0].cpu(), dy.cpu() * (y.cpu() > 0))
 
 
+def test_trunk_epilogues_keep_atens_rule_at_non_finite_values(F):
+    """ReLU's backward in ATen is threshold_backward, `y <= 0 -> 0`: a NaN output PASSES its gradient, and max_pool2d routes dp to the
+    NaN of its window.  The trunk kernels (csrc/trunk.hip) promise the arithmetic of the ops they replace, so one 1 x 8 x 4 x 4
+    channels_last map with a NaN, +inf, -inf, -0.0 and pooling windows that hold a NaN next to a larger finite value, under a zero
+    bias: bias_relu, bias_relu_pool and add_relu forward and backward, and hk_bias_relu_bwd from the byte mask and from the map,
+    against ATen on the CPU bit for bit after nan_to_num; dbias against the float64 column sum of ATen's dx, NaN where that is.
+    On the device ATen's own result is taken there as well and must be the CPU's: the rule is not a property of one backend."""
+    from hawkeye_amd import _lib
+    from hawkeye_amd.functional import ptr, stream
+    nan, inf = float('nan'), float('inf')
+    n, c, h, w = 1, 8, 4, 4
+    gen = torch.Generator().manual_seed(77)
+    x = torch.randn(n, c, h, w, generator=gen).contiguous(memory_format=torch.channels_last)
+    x[0, 0, 0, 0] = nan                                             # a NaN alone among finite values
+    x[0, 1, 1, 2] = inf
+    x[0, 2, 2, 1] = -inf
+    x[0, 3, 0, 3] = -0.0
+    x[0, 4, 2, 2], x[0, 4, 2, 3] = 5.0, nan                         # window (1, 1) of channel 4: the finite 5 first, then the NaN
+    x[0, 5, 2, 2], x[0, 5, 3, 3] = nan, 7.0                         # ... of channel 5: the NaN first, then a larger finite value
+    x[0, 6, 0, 0], x[0, 6, 0, 1] = inf, nan                         # +inf, then a NaN
+    b = torch.zeros(c)
+    dy = torch.randn(n, c, h, w, generator=gen).contiguous(memory_format=torch.channels_last)
+    dp = torch.randn(n, c, h // 2, w // 2, generator=gen).contiguous(memory_format=torch.channels_last)
+    other = torch.randn(n, c, h, w, generator=gen).contiguous(memory_format=torch.channels_last)
+
+    def same(got, ref, what):
+        got, ref = got.detach().cpu(), ref.detach().cpu()
+        assert torch.equal(torch.isnan(got), torch.isnan(ref)), what
+        assert torch.equal(torch.nan_to_num(got, nan=-777.0), torch.nan_to_num(ref, nan=-777.0)), what
+
+    def same_db(got, dx_ref, what):
+        ref = dx_ref.detach().cpu().double().sum((0, 2, 3))
+        got = got.detach().cpu().double()
+        assert torch.equal(torch.isnan(got), torch.isnan(ref)), what
+        fin = torch.isfinite(ref)
+        assert torch.equal(got[~fin].nan_to_num(nan=-777.0), ref[~fin].nan_to_num(nan=-777.0)), what
+        assert rel(got[fin], ref[fin]) < 1e-6, what
+
+    def aten(dev):
+        xr, br = x.clone().to(dev).requires_grad_(True), b.clone().to(dev)
+        yr = torch.relu(xr + br.view(1, -1, 1, 1))
+        yr.backward(dy.to(dev))
+        xp = x.clone().to(dev).requires_grad_(True)
+        pr = torch.nn.functional.max_pool2d(torch.relu(xp + br.view(1, -1, 1, 1)), 2, 2)
+        pr.backward(dp.to(dev))
+        ar, orr = x.clone().to(dev).requires_grad_(True), other.clone().to(dev).requires_grad_(True)
+        sr = torch.relu(ar + orr)
+        sr.backward(dy.to(dev))
+        return [v.detach().cpu() for v in (yr, xr.grad, pr, xp.grad, sr, ar.grad, orr.grad)]
+
+    yr, dxr, pr, dxpr, sr, dar, dor = aten('cpu')
+    # what this test pins, stated on the reference itself: the gradient passes at the NaN outputs and stops at -inf, -0.0
+    assert torch.isnan(yr[0, 0, 0, 0]) and dxr[0, 0, 0, 0] == dy[0, 0, 0, 0] and dxr[0, 1, 1, 2] == dy[0, 1, 1, 2]
+    assert dxr[0, 2, 2, 1] == 0 and dxr[0, 3, 0, 3] == 0
+    assert torch.isnan(pr[0, 4, 1, 1]) and dxpr[0, 4, 2, 3] == dp[0, 4, 1, 1] and dxpr[0, 4, 2, 2] == 0
+    assert torch.isnan(pr[0, 5, 1, 1]) and dxpr[0, 5, 2, 2] == dp[0, 5, 1, 1] and dxpr[0, 5, 3, 3] == 0
+    assert torch.isnan(pr[0, 6, 0, 0]) and dxpr[0, 6, 0, 1] == dp[0, 6, 0, 0] and dxpr[0, 6, 0, 0] == 0
+    if DEV != 'cpu':
+        for i, (on_dev, on_cpu) in enumerate(zip(aten(DEV), (yr, dxr, pr, dxpr, sr, dar, dor))):
+            same(on_dev, on_cpu, ('ATen on the device', i))
+
+    xg, bg = x.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
+    y = F.bias_relu(xg * 1.0, bg)
+    same(y, yr, 'bias_relu forward')
+    y.backward(dy.to(DEV))
+    same(xg.grad, dxr, 'bias_relu backward')
+    same_db(bg.grad, dxr, 'bias_relu dbias')
+    xg, bg = x.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
+    p = F.bias_relu_pool(xg * 1.0, bg)
+    same(p, pr, 'bias_relu_pool forward')
+    p.backward(dp.to(DEV))
+    same(xg.grad, dxpr, 'bias_relu_pool backward')
+    same_db(bg.grad, dxpr, 'bias_relu_pool dbias')
+    ag, og = x.clone().to(DEV).requires_grad_(True), other.clone().to(DEV).requires_grad_(True)
+    s = F.add_relu(ag * 1.0, og)
+    same(s, sr, 'add_relu forward')
+    s.backward(dy.to(DEV))
+    same(ag.grad, dar, 'add_relu backward, first operand')
+    same(og.grad, dor, 'add_relu backward, second operand')
+
+    # hk_bias_relu_bwd itself, the sign taken from the byte mask and from the map (NHWC rows as the kernels see them)
+    lib = _lib.load()
+    rows = n * h * w
+    yk = x.permute(0, 2, 3, 1).contiguous().to(DEV)
+    bk, dyk = b.to(DEV), dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    mask = torch.empty(n, h, w, c // 4, dtype=torch.uint8, device=yk.device)
+    assert lib.hk_bias_relu_fwd(ptr(yk), ptr(bk), ptr(mask), rows, c, stream()) == 0
+    same(yk.permute(0, 3, 1, 2), yr, 'hk_bias_relu_fwd')
+    bits = ((mask.cpu().unsqueeze(-1).int() >> torch.arange(4)) & 1).bool().reshape(n, h, w, c)
+    assert torch.equal(bits, ~(yr.permute(0, 2, 3, 1) <= 0))
+    nws = lib.hk_trunk_ws_bytes(c)
+    ws = torch.empty(nws, dtype=torch.uint8, device=yk.device)
+    for yy, mm, what in ((yk, None, 'from the map'), (None, mask, 'from the mask')):
+        dx, db = torch.full_like(dyk, nan), torch.full((c,), nan, device=yk.device)
+        assert lib.hk_bias_relu_bwd(ptr(dyk), ptr(yy), ptr(mm), ptr(dx), ptr(db), rows, c, ptr(ws), nws, stream()) == 0
+        same(dx.permute(0, 3, 1, 2), dxr, 'hk_bias_relu_bwd ' + what)
+        same_db(db, dxr, 'hk_bias_relu_bwd dbias ' + what)
+
+    # the first convolution writes its sign mask the same way: a NaN pixel makes NaN outputs, whose gradients count in dbias
+    gen = torch.Generator().manual_seed(78)
+    x1 = torch.randn(1, 3, 5, 6, generator=gen).contiguous(memory_format=torch.channels_last)
+    x1[0, 1, 2, 3] = nan
+    w1, b1 = torch.randn(64, 3, 3, 3, generator=gen) * 0.3, torch.randn(64, generator=gen) * 0.2
+    dy1 = torch.randn(1, 64, 5, 6, generator=gen).contiguous(memory_format=torch.channels_last)
+    br1 = b1.clone().requires_grad_(True)
+    yr1 = torch.relu(torch.nn.functional.conv2d(x1, w1, br1, padding=1))
+    yr1.backward(dy1)
+    assert int(torch.isnan(yr1).sum()) == 9 * 64
+    wg1, bg1 = w1.clone().to(DEV).requires_grad_(True), b1.clone().to(DEV).requires_grad_(True)
+    y1 = F.conv1_bias_relu(x1.to(DEV), wg1, bg1)
+    assert torch.equal(torch.isnan(y1).cpu(), torch.isnan(yr1.detach()))
+    y1.backward(dy1.to(DEV))
+    # (the float64 sum takes the sign pattern of the kernel's own float32 output, as test_first_convolution_kernels_at_the_metric_shape
+    #  does: an output within rounding of the kink is the kink, not the rule; the NaN outputs are ATen's, checked above)
+    passes = ~(y1.detach().cpu() <= 0)
+    assert rel(bg1.grad, (dy1.double() * passes).sum((0, 2, 3))) < 1e-5
+    assert rel(br1.grad, (dy1.double() * ~(yr1.detach() <= 0)).sum((0, 2, 3))) < 1e-5          # ATen counts them too
+
+
 @pytest.mark.parametrize('n,cin,h,w', [(2, 3, 9, 13), (1, 3, 64, 64), (2, 2, 5, 7), (3, 1, 4, 4), (1, 3, 1, 5), (2, 3, 20, 70)])
 def test_first_convolution_with_its_epilogue_in_one_kernel(F, n, cin, h, w):
     """hk_conv1_bias_relu_fwd / bwd (the trunk's first layer, Conv2d(Cin <= 4, 64, 3, padding=1) + bias + ReLU of
