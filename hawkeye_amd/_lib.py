@@ -135,11 +135,19 @@ TRUNK_SIGNATURES = {
     'hk_conv3x3_bwd_data': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
 }
 
+# ... with the trunk's epilogue passes inside those kernels; mirrors include/hawkeye_conv_epi.h one to one
+TRUNK_EPI_SIGNATURES = {
+    'hk_conv3x3_bias_relu_fwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_conv3x3_bias_relu_pool_fwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_conv3x3_masked_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    'hk_conv3x3_masked_bwd_data': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
+}
+
 
 def attach(lib):
-    """Give every function of SIGNATURES and TRUNK_SIGNATURES its prototype on a library object (the gfx950 build, or whatever
-    stands in for it).  Returns the library."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()):
+    """Give every function of SIGNATURES, TRUNK_SIGNATURES and TRUNK_EPI_SIGNATURES its prototype on a library object (the gfx950
+    build, or whatever stands in for it).  Returns the library."""
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()) + list(TRUNK_EPI_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args

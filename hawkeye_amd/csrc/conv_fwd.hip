@@ -33,6 +33,12 @@
 //   measured = 175 - 202 TF/s stand-alone at batch 64 where the library's fp32 kernels give 108 - 139; in the training step the twelve
 //              forwards 42.1 ms against 57.5 and the twelve input gradients 40.7 against 59.9, and no zero-fill of an output is left;
 //              matrix pipe 56 - 64 % busy at 1.9 GHz, LDS bank conflicts 7 % of the LDS-active cycles
+//   epilogue = the main kernel is a template (EPI, documented at the kernel): besides the plain store it leaves with bias + ReLU + sign
+//              mask, with bias + ReLU + 2 x 2 max-pool + argmax (the full-resolution map is never written), or - the input gradient -
+//              with the producing layer's ReLU mask applied and that layer's bias gradient summed (fp64 partial row per tile, then
+//              conv3x3_colsum_kernel in two stages).  The same bits as the passes of trunk.hip they replace (the bias gradient: the
+//              float next to the exact sum); in the training step those passes were 4.9 ms of 124.5, the four instantiations take
+//              what the plain kernel took (80.4 against 80.5 ms), the reductions 0.07 ms
 #include "hk_common.h"
 #include "hk_split_bf16.h"
 #include "../../include/hawkeye_hip.h"
@@ -95,11 +101,43 @@ __device__ __forceinline__ bf16x8 cf_frag(const char* p) {
 #endif
 }
 
+constexpr int CF_EPI_NONE = 0, CF_EPI_RELU = 1, CF_EPI_POOL = 2, CF_EPI_MASK = 3;
+constexpr int CF_PARK = CF_CO + 4;                       // floats of a parked pixel (CF_EPI_POOL): 272 B, 16 lanes' float4 on 64 different banks
+constexpr int CF_DB_RPG = 128;                           // partial rows a workgroup of the first reduction stage adds
+static_assert(CF_R * CF_SW * CF_PARK * 4 <= CF_LDS, "the parked tile fits the LDS of the main loop");
+
+__device__ __forceinline__ f32x4 cf_relu4(f32x4 v) {                 // relu4 of trunk.hip
+    f32x4 r;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) r[t] = v[t] < 0.f ? 0.f : v[t];
+    return r;
+}
+__device__ __forceinline__ unsigned cf_sign4(f32x4 r) {             // the mask byte of bias_relu_fwd_kernel<true>
+    return (!(r[0] <= 0.f) ? 1u : 0u) | (!(r[1] <= 0.f) ? 2u : 0u) | (!(r[2] <= 0.f) ? 4u : 0u) | (!(r[3] <= 0.f) ? 8u : 0u);
+}
+
 // x [N][H][W][Cin], ws as conv3x3_wsplit_kernel leaves it -> y [N][H][W][Cout].  grid xcd_grid(ntiles, Cout / 64), dynamic LDS CF_LDS.
 // tile = ((n nrb + rb) nstrips + strip): rows [4 rb, 4 rb + 4), columns [32 strip, 32 strip + 32)
+//
+// EPI, what happens to the accumulators on their way out (the main loop is the same code in all four):
+//   CF_EPI_NONE  y = the sums                                                                    (hk_conv3x3_fwd, hk_conv3x3_bwd_data)
+//   CF_EPI_RELU  y = relu4(sums + bias) and, where mk is given, the sign byte of every channel quad in the [pixel][Cout / 4] layout of
+//                bias_relu_fwd_kernel<true> (trunk.hip).  A lane holds the even (hf = 0) or the odd quads of its pixel: the two
+//                lanes swap their eight bytes and each stores eight consecutive ones
+//   CF_EPI_POOL  y = p [N][H / 2][W / 2][Cout] = maxpool2x2(relu4(sums + bias)), mk = the 2-bit argmax codes, both exactly as
+//                bias_relu_pool_fwd_kernel forms them (H, W even: a tile anchored at multiples of 4 and 32 holds whole windows).  The
+//                full-resolution map is never written: every wave parks its row in the LDS the last tap has left free, and after one
+//                barrier a thread forms two pooled float4; the 16 lanes of a pooled pixel gather their code bytes into two 8-byte stores
+//   CF_EPI_MASK  y = sums where the bit of mk (read: the sign mask of the map this call produces the gradient of) is set, else 0 -
+//                what bias_relu_bwd_kernel<true> writes - and part [tile][Cout] = this workgroup's column sums of those values:
+//                a halving butterfly over the 32 pixels of a wave (31 cross-lane adds a lane, lane l ends with channel slot l), then
+//                the four waves through LDS in wave order
+// bias and mask are read behind the loop: nothing joins the loads its counted waits count
+template <int EPI>
 __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __restrict__ x, const char* __restrict__ ws,
                                                                float* __restrict__ y, int H, int W, int Cin, int Cout, int nstrips,
-                                                               int nrb, int ntiles) {
+                                                               int nrb, int ntiles, const float* __restrict__ bias,
+                                                               uint8_t* __restrict__ mk, double* __restrict__ part) {
     HK_DYN_LDS16(ldsf);
     char* xs = reinterpret_cast<char*>(ldsf);            // the halo tile of the chunk: [piece][6 x 34 pixels][80 B]
     char* wb = xs + 3 * CF_XPLANE;                       // two weight tiles: [buf][piece][64 co][80 B]
@@ -243,23 +281,185 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     }
     // C layout of the 32 x 32 MFMA: column = lane & 31 (pixel), row = 8 (i / 4) + 4 (lane >> 5) + i % 4 (output channel)
     const int row = r0 + wave, col = c0 + l31;
-    if (row < H && col < W) {
-        float* yp = y + ((n * H + row) * W + col) * Cout + cot * CF_CO + 4 * hf;
+    if (EPI == CF_EPI_NONE) {
+        if (row < H && col < W) {
+            float* yp = y + ((n * H + row) * W + col) * Cout + cot * CF_CO + 4 * hf;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = sum[cb][4 * j + e] + acc[cb][4 * j + e];
+                    *reinterpret_cast<f32x4*>(yp + cb * 32 + 8 * j) = v;
+                }
+        }
+        return;
+    }
+    // v[cb][j]: channel quad 8 cb + 2 j + hf of this workgroup's sixteen
+    const bool live = row < H && col < W;
+    const long long pix = (n * H + row) * W + col;                  // (used where live)
+    const int c4 = Cout / 4;
+    f32x4 v[2][4];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[cb][j][e] = sum[cb][4 * j + e] + acc[cb][4 * j + e];
+    if (EPI == CF_EPI_RELU || EPI == CF_EPI_POOL) {
+        const f32x4* b4 = reinterpret_cast<const f32x4*>(bias + cot * CF_CO + 4 * hf);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[cb][j] = cf_relu4(v[cb][j] + b4[8 * cb + 2 * j]);
+    }
+    if (EPI == CF_EPI_RELU) {
+        if (live) {
+            float* yp = y + pix * Cout + cot * CF_CO + 4 * hf;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(yp + cb * 32 + 8 * j) = v[cb][j];
+        }
+        if (mk) {                                                    // (the same for every thread of the launch)
+            unsigned own[2];
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                own[cb] = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) own[cb] |= cf_sign4(v[cb][j]) << (8 * j);
+            }
+            // hf = 0 stores the bytes of quads 0 - 7 (its own even ones, the partner's odd ones of cb = 0), hf = 1 those of 8 - 15
+            const unsigned theirs0 = __shfl_xor(own[0], 32), theirs1 = __shfl_xor(own[1], 32);
+            const unsigned ev = hf ? theirs1 : own[0], od = hf ? own[1] : theirs0;
+            unsigned long long m8 = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                m8 |= ((unsigned long long)((ev >> (8 * k)) & 0xffu) << (16 * k)) | ((unsigned long long)((od >> (8 * k)) & 0xffu) << (16 * k + 8));
+            if (live) *reinterpret_cast<unsigned long long*>(mk + pix * c4 + cot * (CF_CO / 4) + 8 * hf) = m8;
+        }
+    }
+    if (EPI == CF_EPI_POOL) {
+        float* park = ldsf;                                          // [4 rows][32 columns][CF_PARK floats]: every wave is past the last tap's barrier
+        float* mine = park + (wave * CF_SW + l31) * CF_PARK + 4 * hf;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(mine + cb * 32 + 8 * j) = v[cb][j];
+        __syncthreads();
+        const int q = tid & 15, pc = tid >> 4;                       // channel quad, pooled column of the tile; pooled rows u = 0, 1
+        const int Ho = H / 2, Wo = W / 2;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const float* src = park + (2 * u * CF_SW + 2 * pc) * CF_PARK + 4 * q;
+            f32x4 m = *reinterpret_cast<const f32x4*>(src);
+            unsigned code = 0;
+#pragma unroll
+            for (int k = 1; k < 4; ++k) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(src + ((k >> 1) * CF_SW + (k & 1)) * CF_PARK);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const bool take = (a[t] > m[t]) || (a[t] != a[t]);          // ATen max_pool2d: (val > max) || isnan(val)
+                    m[t] = take ? a[t] : m[t];
+                    code = take ? ((code & ~(3u << (2 * t))) | ((unsigned)k << (2 * t))) : code;
+                }
+            }
+            // the code bytes of quads 8 (q / 8) ..+7 of this pooled pixel, gathered from their eight lanes, in every one of them
+            unsigned t1 = __shfl_xor(code, 1);
+            unsigned c2 = (q & 1) ? (t1 | (code << 8)) : (code | (t1 << 8));
+            unsigned t2 = __shfl_xor(c2, 2);
+            unsigned c4b = (q & 2) ? (t2 | (c2 << 16)) : (c2 | (t2 << 16));
+            unsigned t4 = __shfl_xor(c4b, 4);
+            const unsigned long long lo = (q & 4) ? t4 : c4b, hi = (q & 4) ? c4b : t4;
+            const int ho = r0 / 2 + u, wo = c0 / 2 + pc;
+            if (ho < Ho && wo < Wo) {
+                const long long opix = (n * Ho + ho) * Wo + wo;
+                *reinterpret_cast<f32x4*>(y + opix * Cout + cot * CF_CO + 4 * q) = m;
+                if ((q & 7) == 0) *reinterpret_cast<unsigned long long*>(mk + opix * c4 + cot * (CF_CO / 4) + q) = lo | (hi << 32);
+            }
+        }
+    }
+    if (EPI == CF_EPI_MASK) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 mb = {0u, 0u, 0u, 0u};                                 // the 16 sign bytes of this pixel's quads; none past the image: zeros there
+        if (live) mb = *reinterpret_cast<const u32x4*>(mk + pix * c4 + cot * (CF_CO / 4));
+        double s[32];                                                // (fp64 from here to db: see conv3x3_colsum_kernel)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                f32x4 v;
+                const unsigned bits = mb[2 * cb + (j >> 1)] >> (8 * (2 * (j & 1) + hf));          // byte 2 (4 cb + j) + hf
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = sum[cb][4 * j + e] + acc[cb][4 * j + e];
-                *reinterpret_cast<f32x4*>(yp + cb * 32 + 8 * j) = v;
+                for (int e = 0; e < 4; ++e) {
+                    v[cb][j][e] = ((bits >> e) & 1u) != 0u ? v[cb][j][e] : 0.f;                   // (bias_relu_bwd_kernel: a select, not a product)
+                    s[16 * cb + 4 * j + e] = v[cb][j][e];
+                }
             }
+        if (live) {
+            float* yp = y + pix * Cout + cot * CF_CO + 4 * hf;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(yp + cb * 32 + 8 * j) = v[cb][j];
+        }
+        // column sums over the wave's 32 pixels: at distance d a lane keeps the half of its slots that matches its bit d and adds the
+        // partner's values of that half; slot k of the 32 ends in lane l31 = k
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) {
+            const bool up = (l31 & d) != 0;
+#pragma unroll
+            for (int i = 0; i < d; ++i) {
+                const double send = up ? s[i] : s[i + d], keep = up ? s[i + d] : s[i];
+                s[i] = keep + __shfl_xor(send, d);
+            }
+        }
+        // slot k = 16 cb + 4 j + e is channel 32 cb + 8 j + 4 hf + e of the 64
+        double* red = reinterpret_cast<double*>(ldsf);               // [wave][64 channels]
+        red[wave * CF_CO + 32 * (l31 >> 4) + 8 * ((l31 >> 2) & 3) + 4 * hf + (l31 & 3)] = s[0];
+        __syncthreads();
+        if (tid < CF_CO)
+            part[(long long)tile * Cout + cot * CF_CO + tid] = ((red[tid] + red[CF_CO + tid]) + red[2 * CF_CO + tid]) + red[3 * CF_CO + tid];
     }
 }
 
-// x [N][H][W][K] (*) w -> y [N][H][W][M]: the pre-pass and the main kernel; M, K multiples of 64
+// part [nrows][nel] -> out [gridDim.y][nel]: group g = blockIdx.y adds rows [g rpg, (g + 1) rpg) in a fixed order, as partial_sum_kernel
+// (hk_partial_sum.h) does for all rows - the first stage (OUT = double) spreads up to 25088 partial rows (25.7 MB) over the chip, the
+// second (OUT = float) adds the groups' rows.  The column sums stay fp64 from the wave's butterfly to here and are rounded ONCE, by the
+// second stage's store: db is the float next to the exact sum whatever the order of the additions was (the two-kernel path's fp32
+// chain of up to 12.8 M additions is one of the floats further away, or the same one)
+template <int Q, typename OUT>
+__global__ __launch_bounds__(64 * Q) void conv3x3_colsum_kernel(const double* __restrict__ part, int nrows, int nel, int rpg,
+                                                                OUT* __restrict__ out) {
+    __shared__ double red[Q][64];
+    const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + l;
+    const int beg = blockIdx.y * rpg, end = beg + rpg < nrows ? beg + rpg : nrows;
+    double s = 0.0;
+    if (e < nel) {
+        int k = beg + q;
+        for (; k + 7 * Q < end; k += 8 * Q) {
+            double t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t[u] = part[(long long)(k + Q * u) * nel + e];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += t[u];
+        }
+        for (; k < end; k += Q) s += part[(long long)k * nel + e];
+    }
+    red[q][l] = s;
+    __syncthreads();
+    if (q == 0 && e < nel) {
+        double t = red[0][l];
+        for (int k = 1; k < Q; ++k) t += red[k][l];
+        out[(long long)blockIdx.y * nel + e] = (OUT)t;
+    }
+}
+
+// x [N][H][W][K] (*) w -> y [N][H][W][M] (or what EPI makes of it): the pre-pass and the main kernel; M, K multiples of 64
+template <int EPI>
 static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
-                       hipStream_t stream) {
+                       hipStream_t stream, const float* bias = nullptr, uint8_t* mk = nullptr, double* part = nullptr) {
     const long long nstrips = ((long long)W + CF_SW - 1) / CF_SW, nrb = ((long long)H + CF_R - 1) / CF_R, ntiles = N * nrb * nstrips;
     const int ncot = M / CF_CO;
     if ((ntiles + NXCD) * ncot > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
@@ -267,9 +467,9 @@ static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, i
     hipLaunchKernelGGL(conv3x3_wsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (char*)ws, M, K,
                        transposed ? 1 : 0, total);
     HK_LAUNCH_CHECK();
-    HK_ALLOW_BIG_LDS(conv3x3_split_kernel, CF_LDS);
-    hipLaunchKernelGGL(conv3x3_split_kernel, dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), CF_LDS, stream, x, (const char*)ws, y,
-                       H, W, K, M, (int)nstrips, (int)nrb, (int)ntiles);
+    HK_ALLOW_BIG_LDS(conv3x3_split_kernel<EPI>, CF_LDS);
+    hipLaunchKernelGGL(conv3x3_split_kernel<EPI>, dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), CF_LDS, stream, x, (const char*)ws,
+                       y, H, W, K, M, (int)nstrips, (int)nrb, (int)ntiles, bias, mk, part);
     HK_LAUNCH_CHECK();
     return HK_OK;
 }
@@ -284,6 +484,12 @@ static int conv3x3_check(const float* x, const float* w, float* y, int N, int H,
     return HK_OK;
 }
 
+// tiles of a map (= partial rows of the masked input gradient) and the groups the first reduction stage makes of them
+static long long conv3x3_tiles(int N, int H, int W) {
+    return (long long)N * (((long long)H + CF_R - 1) / CF_R) * (((long long)W + CF_SW - 1) / CF_SW);
+}
+static long long conv3x3_groups(long long ntiles) { return ntiles > CF_DB_RPG ? (ntiles + CF_DB_RPG - 1) / CF_DB_RPG : 0; }
+
 }  // namespace hk
 
 using namespace hk;
@@ -297,11 +503,63 @@ extern "C" size_t hk_conv3x3_ws_bytes(int Cin, int Cout) {          // (for any 
 extern "C" int hk_conv3x3_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
                               hk_stream_t stream) {
     const int rc = conv3x3_check(x, w, y, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_fwd);
-    return rc != HK_OK ? rc : conv3x3_run(x, w, y, N, H, W, Cin, Cout, false, ws, (hipStream_t)stream);
+    return rc != HK_OK ? rc : conv3x3_run<CF_EPI_NONE>(x, w, y, N, H, W, Cin, Cout, false, ws, (hipStream_t)stream);
 }
 
 extern "C" int hk_conv3x3_bwd_data(const float* dy, const float* w, float* dx, int N, int H, int W, int Cin, int Cout, void* ws,
                                    size_t ws_bytes, hk_stream_t stream) {
     const int rc = conv3x3_check(dy, w, dx, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_bwd_data);
-    return rc != HK_OK ? rc : conv3x3_run(dy, w, dx, N, H, W, Cout, Cin, true, ws, (hipStream_t)stream);
+    return rc != HK_OK ? rc : conv3x3_run<CF_EPI_NONE>(dy, w, dx, N, H, W, Cout, Cin, true, ws, (hipStream_t)stream);
+}
+
+extern "C" int hk_conv3x3_bias_relu_fwd(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int N, int H, int W,
+                                        int Cin, int Cout, void* ws, size_t ws_bytes, hk_stream_t stream) {
+    if (!bias) return HK_ERR_BAD_ARG;
+    const int rc = conv3x3_check(x, w, y, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_fwd);
+    if (rc != HK_OK) return rc;
+    if (!aligned16(bias) || (((uintptr_t)mask) & 7) != 0 || tuning().conv_epi < 1) return HK_ERR_UNSUPPORTED;
+    return conv3x3_run<CF_EPI_RELU>(x, w, y, N, H, W, Cin, Cout, false, ws, (hipStream_t)stream, bias, mask);
+}
+
+extern "C" int hk_conv3x3_bias_relu_pool_fwd(const float* x, const float* w, const float* bias, float* p, uint8_t* argmax, int N, int H,
+                                             int W, int Cin, int Cout, void* ws, size_t ws_bytes, hk_stream_t stream) {
+    if (!bias || !argmax) return HK_ERR_BAD_ARG;
+    const int rc = conv3x3_check(x, w, p, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_fwd);
+    if (rc != HK_OK) return rc;
+    if (H % 2 != 0 || W % 2 != 0 || !aligned16(bias) || (((uintptr_t)argmax) & 7) != 0 || tuning().conv_epi < 1) return HK_ERR_UNSUPPORTED;
+    return conv3x3_run<CF_EPI_POOL>(x, w, p, N, H, W, Cin, Cout, false, ws, (hipStream_t)stream, bias, argmax);
+}
+
+extern "C" size_t hk_conv3x3_masked_ws_bytes(int N, int H, int W, int Cin, int Cout) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    const long long ntiles = conv3x3_tiles(N, H, W);
+    return hk_conv3x3_ws_bytes(Cin, Cout) + (size_t)(ntiles + conv3x3_groups(ntiles)) * Cin * sizeof(double);
+}
+
+extern "C" int hk_conv3x3_masked_bwd_data(const float* dy, const float* w, const uint8_t* mask, float* dx, float* dbias, int N, int H, int W,
+                                          int Cin, int Cout, void* ws, size_t ws_bytes, hk_stream_t stream) {
+    if (!mask || !dbias) return HK_ERR_BAD_ARG;
+    const int rc = conv3x3_check(dy, w, dx, N, H, W, Cin, Cout, ws, ws_bytes, tuning().conv_bwd_data);
+    if (rc != HK_OK) return rc;
+    if (ws_bytes < hk_conv3x3_masked_ws_bytes(N, H, W, Cin, Cout)) return HK_ERR_WORKSPACE;
+    if (!aligned16(mask) || tuning().conv_epi < 2) return HK_ERR_UNSUPPORTED;
+    const long long ntiles = conv3x3_tiles(N, H, W), ngroups = conv3x3_groups(ntiles);
+    if (ntiles > 0x7fffffffll || ngroups > 65535) return HK_ERR_UNSUPPORTED;
+    double* part = reinterpret_cast<double*>((char*)ws + hk_conv3x3_ws_bytes(Cin, Cout));    // [ntiles][Cin], then [ngroups][Cin]
+    double* grp = part + ntiles * Cin;
+    const int rc2 = conv3x3_run<CF_EPI_MASK>(dy, w, dx, N, H, W, Cout, Cin, true, ws, (hipStream_t)stream, nullptr, const_cast<uint8_t*>(mask), part);
+    if (rc2 != HK_OK) return rc2;
+    const dim3 cols((unsigned)(Cin / 64));
+    if (ngroups > 0) {
+        hipLaunchKernelGGL((conv3x3_colsum_kernel<16, double>), dim3(cols.x, (unsigned)ngroups), dim3(1024), 0, (hipStream_t)stream,
+                           (const double*)part, (int)ntiles, Cin, CF_DB_RPG, grp);
+        HK_LAUNCH_CHECK();
+        hipLaunchKernelGGL((conv3x3_colsum_kernel<16, float>), cols, dim3(1024), 0, (hipStream_t)stream, (const double*)grp, (int)ngroups, Cin,
+                           (int)ngroups, dbias);
+    } else {
+        hipLaunchKernelGGL((conv3x3_colsum_kernel<16, float>), cols, dim3(1024), 0, (hipStream_t)stream, (const double*)part, (int)ntiles, Cin,
+                           (int)ntiles, dbias);
+    }
+    HK_LAUNCH_CHECK();
+    return HK_OK;
 }

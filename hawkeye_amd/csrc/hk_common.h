@@ -66,6 +66,9 @@ struct Tuning {
                             //                  measured table (functional.CONV_FWD_WINS), 0: the library's everywhere (the entry point refuses), 1: hk_conv3x3_fwd
                             //                  wherever it serves the call (tests)
     int conv_bwd_data = -1; // HK_CONV_BWD_DATA the same for their input gradient: hk_conv3x3_bwd_data, functional.CONV_BWD_DATA_WINS
+    int conv_epi = 2;       // HK_CONV_EPI      epilogues of those kernels (conv_fwd.hip, EPI): 0: none - bias, ReLU, pool and the ReLU backward stay the
+                            //                  passes of trunk.hip, 1: bias + ReLU (+ pool) inside the forward, 2: and the producer's sign mask and
+                            //                  bias-gradient partials inside the input gradient (the entry points refuse below their level)
     int peer_form = 0;      // HK_PEER_FORM     hk_peer_loss: 0: automatic - the one-launch LDS-resident form wherever both logit matrices fit one
                             //                  workgroup's LDS (by launch count: NOT yet timed on the device), 1: the three-launch general form,
                             //                  2: the resident form or HK_ERR_UNSUPPORTED

@@ -6,6 +6,8 @@ Outputs and workspaces are allocated through torch's caching allocator; kernels
 are enqueued on torch's current HIP stream; nothing synchronises the host.
 fp32 only, HIP tensors only - there is no CPU fallback (see hawkeye_amd/_lib.py).
 """
+import threading
+
 import numpy as np
 import torch
 
@@ -2053,13 +2055,173 @@ class _Conv3x3(torch.autograd.Function):
 
 
 def conv3x3(x, weight, fwd=False, bwd=False, wrw=True):
-    """conv2d(x, weight, None, stride=1, padding=1) with the chosen GEMMs on the project's kernels; see _Conv3x3."""
+    """conv2d(x, weight, None, stride=1, padding=1) with the chosen GEMMs on the project's kernels; see _Conv3x3.  Inside a
+    ConvEpilogue context (and with `fwd`): the fused unit it asks for, see _ConvUnit."""
+    e = ConvEpilogue.take()
+    if e is not None:
+        if not fwd:
+            raise _lib.HawkeyeHipError('conv3x3: an epilogue inside the kernel needs the forward on the kernel (fwd)')
+        return _ConvUnit.apply(x, weight, e.bias, e.pool, bool(bwd), bool(wrw), e.masked, e.link_in, e.link)
     return _Conv3x3.apply(x, weight, bool(fwd), bool(bwd), bool(wrw))
 
 
 def conv3x3_wrw(x, weight):
     """conv2d(x, weight, None, stride=1, padding=1) with the weight gradient on hk_conv3x3_wrw; see _Conv3x3."""
     return _Conv3x3.apply(x, weight, False, False, True)
+
+
+# The layers whose forward runs with its epilogue inside the kernel (hk_conv3x3_bias_relu_fwd / hk_conv3x3_bias_relu_pool_fwd) and
+# whose input gradient takes the producing layer's mask (hk_conv3x3_masked_bwd_data), knob `conv_epi` at its default 2: the layers of
+# CONV_FWD_WINS / CONV_BWD_DATA_WINS for which the fused form was not measured SLOWER than its two-kernel pair inside the training
+# step (DESIGN 3.10, "Epilogues inside the kernels").  A layer listed here is taken out of the fusion, not out of the kernel.
+CONV_EPI_FWD_LOSES = {}
+CONV_EPI_MASKED_LOSES = {}
+
+
+def conv3x3_epi_level():
+    """Knob `conv_epi`: 0 the epilogues of the trunk's convolutions as passes of their own, 1 bias + ReLU (+ pool) inside the forward
+    kernel, 2 (default) also the producer's ReLU mask and bias-gradient partials inside the input-gradient kernel."""
+    return _knob(b'conv_epi')
+
+
+def conv3x3_epi_fwd_ok(x, conv, fwd):
+    """Whether a layer whose forward runs on hk_conv3x3_fwd (`fwd` = conv3x3_fwd_ok) runs it with bias + ReLU (+ pool) inside:
+    `conv_epi` >= 1, a bias, and a channel count the epilogues' backward passes serve (trunk_epilogue_ok's rule)."""
+    c = conv.out_channels
+    return bool(fwd and conv3x3_epi_level() >= 1 and conv.bias is not None and conv.bias.dtype == torch.float32
+                and conv.bias.data_ptr() % 16 == 0 and 256 % (c // 4) == 0
+                and x.shape[0] not in CONV_EPI_FWD_LOSES.get((conv.in_channels, c, x.shape[2], x.shape[3]), ()))
+
+
+def conv3x3_epi_masked_ok(x, conv, bwd):
+    """Whether a layer whose input gradient runs on hk_conv3x3_bwd_data (`bwd` = conv3x3_bwd_data_ok) applies the mask of the layer
+    that produced x inside that kernel, given such a mask: `conv_epi` == 2."""
+    return bool(bwd and conv3x3_epi_level() >= 2
+                and x.shape[0] not in CONV_EPI_MASKED_LOSES.get((conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]), ()))
+
+
+class ConvLink:
+    """What one fused unit of the trunk hands the next (model/backbone/vgg.py: ConvStack.forward) beside its output: `mask`, the sign
+    mask of that output ([N][H][W][C / 4] bytes; None behind a pool and behind an unfused layer).  In the backward pass the CONSUMING
+    unit, if its input gradient runs on hk_conv3x3_masked_bwd_data, applies the mask itself and leaves `db`, the producer's bias
+    gradient, here; the producer then finds its incoming gradient already masked and skips hk_bias_relu_bwd.  The contract - the
+    gradient that travels between two linked units is the MASKED one - holds only where nobody else can see that tensor: inside
+    ConvStack.forward."""
+    __slots__ = ('mask', 'db')
+
+    def __init__(self, mask=None):
+        self.mask, self.db = mask, None
+
+
+class _ConvUnit(torch.autograd.Function):
+    """One layer of the trunk as ONE node: relu(conv2d(x, weight, bias, padding 1)), or its 2 x 2 max-pool, with the epilogue inside the
+    forward kernel (csrc/conv_fwd.hip, EPI).  Backward: the epilogue's backward pass (hk_bias_relu_pool_bwd, or hk_bias_relu_bwd
+    unless the consumer has applied this layer's mask already: ConvLink), then the two gradients as _Conv3x3 routes them, the input
+    gradient with the producer's mask where `link_in` carries one and `masked` says so."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pool, bwd, wrw, masked, link_in, link_out):
+        lib = _lib.load()
+        _nhwc(x, 'conv3x3 unit')
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        if (tuple(weight.shape) != (cout, cin, 3, 3) or not weight.is_contiguous(memory_format=torch.channels_last)
+                or weight.dtype != torch.float32 or weight.device != x.device):
+            raise _lib.HawkeyeHipError(f'conv3x3 unit: wants a channels_last fp32 [Cout, {cin}, 3, 3] weight on {x.device}, got {weight.dtype} {tuple(weight.shape)}')
+        b = _f32c(bias)
+        px, pw = ptr(x), ptr(weight)
+        nws = lib.hk_conv3x3_ws_bytes(cin, cout)
+        ws = _ws(nws, x.device)
+        grad = any(ctx.needs_input_grad[:3])
+        if pool:
+            y = torch.empty((n, cout, h // 2, w // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            aux = torch.empty(n, h // 2, w // 2, cout // 4, dtype=torch.uint8, device=x.device)
+            check(lib.hk_conv3x3_bias_relu_pool_fwd(px, pw, ptr(b), ptr(y), ptr(aux), n, h, w, cin, cout, ptr(ws), nws, stream()),
+                  'hk_conv3x3_bias_relu_pool_fwd')
+        else:
+            y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            aux = torch.empty(n, h, w, cout // 4, dtype=torch.uint8, device=x.device) if grad else None
+            check(lib.hk_conv3x3_bias_relu_fwd(px, pw, ptr(b), ptr(y), ptr(aux), n, h, w, cin, cout, ptr(ws), nws, stream()),
+                  'hk_conv3x3_bias_relu_fwd')
+            link_out.mask = aux
+        min_ = link_in.mask if (masked and link_in is not None) else None
+        ctx.save_for_backward(x, weight, aux, y if pool else None, min_)
+        ctx.cfg = (pool, bwd, wrw, (n, cout, h, w))
+        ctx.links = (link_in, link_out)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, weight, aux, p, min_ = ctx.saved_tensors
+        pool, bwd, wrw, (n, cout, h, w) = ctx.cfg
+        link_in, link_out = ctx.links
+        cin = x.shape[1]
+        if dy.dtype != torch.float32:
+            raise _lib.HawkeyeHipError(f'conv3x3 unit backward: fp32 only, got {dy.dtype}')
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        db, link_out.db = link_out.db, None
+        if pool:
+            g = torch.empty(n, cout, h, w, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            db = torch.empty(cout, dtype=torch.float32, device=x.device)
+            nws = lib.hk_trunk_ws_bytes(cout)
+            ws = _ws(nws, x.device)
+            check(lib.hk_bias_relu_pool_bwd(ptr(dy), ptr(p), ptr(aux), ptr(g), ptr(db), n, h, w, cout, ptr(ws), nws, stream()),
+                  'hk_bias_relu_pool_bwd')
+        elif db is not None:
+            g = dy                                         # the consumer wrote dy o mask and summed its columns (ConvLink)
+        else:
+            g = torch.empty_like(dy, memory_format=torch.channels_last)
+            db = torch.empty(cout, dtype=torch.float32, device=x.device)
+            nws = lib.hk_trunk_ws_bytes(cout)
+            ws = _ws(nws, x.device)
+            check(lib.hk_bias_relu_bwd(ptr(dy), None, ptr(aux), ptr(g), ptr(db), n * h * w, cout, ptr(ws), nws, stream()),
+                  'hk_bias_relu_bwd')
+        dx = dw = None
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if need_dx and bwd:
+            if min_ is not None:
+                dx = torch.empty_like(x, memory_format=torch.channels_last)
+                dbp = torch.empty(cin, dtype=torch.float32, device=x.device)
+                nws = lib.hk_conv3x3_masked_ws_bytes(n, h, w, cin, cout)
+                ws = _ws(nws, x.device)
+                check(lib.hk_conv3x3_masked_bwd_data(ptr(g), ptr(weight), ptr(min_), ptr(dx), ptr(dbp), n, h, w, cin, cout, ptr(ws), nws,
+                                                     stream()), 'hk_conv3x3_masked_bwd_data')
+                link_in.db = dbp
+            else:
+                dx = conv3x3_bwd_data_raw(g, weight)
+        if need_dw and wrw:
+            dw = conv3x3_wrw_raw(x, g)
+        lib_mask = (need_dx and not bwd, need_dw and not wrw, False)
+        if lib_mask[0] or lib_mask[1]:
+            r = torch.ops.aten.convolution_backward(g, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, lib_mask)
+            dx = r[0] if lib_mask[0] else dx
+            dw = r[1] if lib_mask[1] else dw
+        return dx, dw, (db if ctx.needs_input_grad[2] else None), None, None, None, None, None, None
+
+
+class ConvEpilogue:
+    """`with ConvEpilogue(bias, pool, masked, link_in) as e: y = conv3x3(x, weight, True, bwd, wrw)` - the conv3x3 call inside runs as
+    ONE fused unit (_ConvUnit): y is relu(conv + bias), or its 2 x 2 max-pool, and e.link is the ConvLink for the next unit.  (The
+    request reaches conv3x3 beside its arguments, per thread, so that the call itself stays the one every routed layer makes.)"""
+    _pending = threading.local()
+
+    def __init__(self, bias, pool, masked, link_in):
+        self.bias, self.pool, self.masked, self.link_in, self.link = bias, bool(pool), bool(masked), link_in, ConvLink()
+
+    def __enter__(self):
+        ConvEpilogue._pending.request = self
+        return self
+
+    def __exit__(self, *exc):
+        ConvEpilogue._pending.request = None
+        return False
+
+    @staticmethod
+    def take():
+        e = getattr(ConvEpilogue._pending, 'request', None)
+        ConvEpilogue._pending.request = None
+        return e
 
 
 def bias_relu(x, bias):

@@ -30,7 +30,10 @@ class ConvStack(nn.Sequential):
     gradient of the layers whose input channel count is a multiple of 64 and that functional.conv3x3_wrw_route sends to hk_conv3x3_wrw (csrc/conv_wrw.hip):
     the two 64-input-channel layers at any size, and the ten wider layers of VGG-16 at the map and batch sizes at which the kernel
     was measured faster than the library's (a 448 x 448 input at batch 64 or 16: all ten; any other size stays on the library until it
-    is measured).  Anything the kernels do not cover - CPU tensors, NCHW
+    is measured).  Where a layer's forward runs on hk_conv3x3_fwd's kernel, bias, ReLU and pool happen inside it, and the input
+    gradient of the next such layer applies this layer's ReLU mask and sums its bias gradient (functional._ConvUnit / ConvLink, knob
+    `conv_epi`): the hk_bias_relu_* passes stay for the layers on the library's forward and for the pool backward.
+    Anything the kernels do not cover - CPU tensors, NCHW
     memory, odd map sizes, other dtypes, a child with forward hooks - runs the children one by one as nn.Sequential does."""
 
     def forward(self, x):
@@ -41,8 +44,10 @@ class ConvStack(nn.Sequential):
                 and x.is_contiguous(memory_format=torch.channels_last)) or any(_hooked(m) for m in mods):
             return super().forward(x)
         i = 0
+        link = None         # HF.ConvLink of the unit that produced x: the sign mask of x, where a fused unit wrote one
         while i < len(mods):
             m = mods[i]
+            link_in, link = link, None
             if (isinstance(m, nn.Conv2d) and m.bias is not None and m.padding_mode == 'zeros' and i + 1 < len(mods)
                     and isinstance(mods[i + 1], nn.ReLU)):
                 if not (i + 2 < len(mods) and _plain_pool(mods[i + 2])) and HF.conv1_ok(x, m):
@@ -51,6 +56,17 @@ class ConvStack(nn.Sequential):
                     i += 2
                     continue
                 fwd, bwd, wrw = HF.conv3x3_fwd_ok(x, m), HF.conv3x3_bwd_data_ok(x, m), HF.conv3x3_wrw_ok(x, m)
+                if HF.conv3x3_epi_fwd_ok(x, m, fwd):
+                    # convolution + bias + ReLU (+ pool) as ONE unit, the epilogue inside the forward kernel; its input gradient takes
+                    # the producer's mask along where the producer was such a unit (HF.ConvLink: the gradient between the two is
+                    # then the masked one, which nobody outside this loop can see)
+                    pool = (i + 2 < len(mods) and _plain_pool(mods[i + 2]) and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)
+                    masked = link_in is not None and link_in.mask is not None and HF.conv3x3_epi_masked_ok(x, m, bwd)
+                    with HF.ConvEpilogue(m.bias, pool, masked, link_in) as unit:
+                        x = HF.conv3x3(x, m.weight, fwd, bwd, wrw)
+                    link = unit.link
+                    i += 3 if pool else 2
+                    continue
                 if fwd or bwd or wrw:
                     # a multiple of 64 channels, a routed layer: each of the three GEMMs on its own kernel where it was measured faster
                     # (hk_conv3x3_fwd, hk_conv3x3_bwd_data, hk_conv3x3_wrw), the library's otherwise

@@ -23,7 +23,9 @@ extern "C" {
  * zero-fill is needed, and nothing outside the three tensors and the workspace is read or written.
  * HK_ERR_BAD_ARG for a null pointer or a size < 1, then HK_ERR_WORKSPACE for a missing or short workspace, then
  * HK_ERR_UNSUPPORTED for other channel counts, a misaligned pointer, sizes the kernel's indices cannot address, or the knob
- * "conv_fwd" (hk_conv3x3_bwd_data: "conv_bwd_data") at 0. */
+ * "conv_fwd" (hk_conv3x3_bwd_data: "conv_bwd_data") at 0.
+ * The forms of these two calls that also do the trunk's bias / ReLU / pool / mask passes on the accumulators are declared with those
+ * passes, in hawkeye_conv_epi.h (hk_conv3x3_bias_relu_fwd, hk_conv3x3_bias_relu_pool_fwd, hk_conv3x3_masked_bwd_data). */
 size_t hk_conv3x3_ws_bytes(int Cin, int Cout);
 int hk_conv3x3_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
                    hk_stream_t stream);

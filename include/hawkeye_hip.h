@@ -75,6 +75,8 @@ const char* hk_version(void);
  *                   bf16-MFMA kernel for the layers of the measured table, 0 = the library's everywhere (the entry point then refuses
  *                   with HK_ERR_UNSUPPORTED), 1 = the kernel wherever the entry point serves the call (tests)
  *   "conv_bwd_data" the same for the input gradient of those convolutions
+ *   "conv_epi"      epilogues inside those kernels: 2 (default) = bias + ReLU (+ pool) in the forward and the producing layer's ReLU
+ *                   mask + bias-gradient partials in the input gradient, 1 = the forward ones only, 0 = none (separate passes)
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
@@ -666,5 +668,6 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 #endif
 
 #include "hawkeye_conv.h" /* the trunk's forward and input gradient */
+#include "hawkeye_conv_epi.h" /* ... with the trunk's epilogue passes done inside those kernels */
 
 #endif /* HAWKEYE_HIP_H */
