@@ -204,7 +204,8 @@ def ptr(t):
 
 class tuning:
     """`with tuning(ns_tn=64, bcnn_generic=1): ...` - flips A/B knobs of the library (hk_tuning_set) for tests and
-    benchmarks and restores the previous values on exit.  Not used by the product path."""
+    benchmarks and restores the previous values on exit.  The product path uses it for one knob only: `conv_mfma`, around a call of
+    the trunk's 3 x 3 kernels that its measured table routes to the 16 x 16 x 32 MFMA (functional._conv3x3_mfma)."""
 
     def __init__(self, **knobs):
         self.knobs = knobs

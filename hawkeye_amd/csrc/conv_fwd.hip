@@ -39,8 +39,16 @@
 //              conv3x3_colsum_kernel in two stages).  The same bits as the passes of trunk.hip they replace (the bias gradient: the
 //              float next to the exact sum); in the training step those passes were 4.9 ms of 124.5, the four instantiations take
 //              what the plain kernel took (80.4 against 80.5 ms), the reductions 0.07 ms
+//   MFMA     = a second template parameter (MF, documented at the constants and at the kernel; knob `conv_mfma`): the same tile, chunk,
+//              products, chains and pipeline on v_mfma_f32_16x16x32_bf16, whose fragment wants another LDS image (64-byte pitch, the
+//              k-group pairs of every other four rows swapped: static_asserted conflict-free for all four ds_read_b128 lane groups at
+//              every pixel offset, 63744 B).  Measured at batch 64 ("The MFMA shape"): 196 - 227 TF/s stand-alone where the
+//              other shape gives 177 - 205; in the step the 24 launches 70.2 ms against 80.2 with every layer on it; per launch 9 - 11 %
+//              fewer cycles (LDS bank conflicts 7 % -> 0, a fifth less weight traffic) at a 3 - 4 % higher clock, the matrix pipe
+//              61 - 72 % busy.  Routed per layer, direction and batch by functional.py's measured table; MF = 0 is the code as it was
 #include "hk_common.h"
 #include "hk_split_bf16.h"
+#include <hk_mfma_bf16.h>   // the 16 x 16 x 32 bf16 MFMA (the emulation build finds its model of it first)
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -60,15 +68,56 @@ constexpr int CF_XF4 = CF_HPIX * (CF_CK / 4);            // 1632 float4 of a hal
 constexpr int CF_XU = (CF_XF4 + 255) / 256;              // 7 loads per thread (the last one for 96 threads)
 constexpr int CF_FLUSH = 3;                              // chunks (K = 864) an accumulator chain runs
 
+// MF, the bf16 MFMA the main kernel runs on: CF_MF_32 = v_mfma_f32_32x32x16_bf16 (two 32 x 32 blocks a wave, two k steps a chunk) on
+// the planes above; CF_MF_16 = v_mfma_f32_16x16x32_bf16 (four 16-channel x two 16-pixel blocks a wave, one k step a chunk) on the
+// planes below.  Same tile, chunk, products, chains and pipeline; what differs is the fragment - lane l supplies the eight k at
+// 8 (l / 16) of row or column l % 16 - and with it the image that ds_read_b128 reads without conflicts, and the accumulators' layout
+constexpr int CF_MF_32 = 0, CF_MF_16 = 1;
+constexpr int CF16_PIX = 64;                             // bytes of a pixel (or of a weight row) in a CF_MF_16 plane: 32 bf16, no padding
+constexpr int CF16_XPLANE = CF_HPIX * CF16_PIX;          // 13056 B
+constexpr int CF16_WPLANE = CF_CO * CF16_PIX;            // 4096 B
+constexpr int CF16_WTAP = 3 * CF16_WPLANE;               // 12288 B: three 16-byte loads a thread
+constexpr int CF16_LDS = 3 * CF16_XPLANE + 2 * CF16_WTAP;  // 63744 B
+// THE image of a CF_MF_16 plane, for the staging stores, the fragment reads and the weight pre-pass: byte offset of k-group kg
+// (eight k, 16 bytes) of row `row` (a pixel of the halo tile, or a weight row).  The 80-byte pitch of the other shape puts rows 1
+// and 4 of a ds_read_b128 lane group on one slot; no plain pitch separates the groups, and on the 80-byte pitch no XOR of period 16
+// on the k-group does at every pixel offset (searched; the x fragment starts at any pixel: a tap is an address offset).  Rows 4 apart share their four
+// slots at this pitch; of such rows a lane group reads r (k-group g), r + 4, r + 8 (g ^ 1) and r + 12 (g): swapping the k-group
+// pairs of every other four rows gives them four different slots, whatever r is
+__host__ __device__ constexpr int cf16_off(int row, int kg) { return row * CF16_PIX + ((kg ^ ((row >> 1) & 2)) << 4); }
+// the 16-lane groups of ds_read_b128, one LDS cycle each: a group is conflict-free iff its lanes' 16-byte slots mod 256 B differ
+constexpr int CF_B128_GROUPS[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                       {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
+                                       {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
+                                       {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+constexpr bool cf16_group_conflict_free(int g) {
+    for (int base = 0; base + 16 <= CF_HPIX; ++base) {    // the fragment's first row: any pixel of the halo tile (weights: multiples of 16)
+        unsigned seen = 0;
+        for (int i = 0; i < 16; ++i) {
+            const int lane = CF_B128_GROUPS[g][i], slot = (cf16_off(base + (lane & 15), lane >> 4) >> 4) & 15;
+            if ((seen >> slot) & 1u) return false;
+            seen |= 1u << slot;
+        }
+    }
+    return true;
+}
+static_assert(cf16_group_conflict_free(0) && cf16_group_conflict_free(1) && cf16_group_conflict_free(2) && cf16_group_conflict_free(3),
+              "every ds_read_b128 lane group of a CF_MF_16 fragment reads 16 different slots");
+static_assert(cf16_off(16, 1) == cf16_off(0, 1) + 16 * CF16_PIX && cf16_off(35, 2) == cf16_off(3, 2) + 32 * CF16_PIX,
+              "rows 16 and 32 further on are a constant offset away");
+static_assert(CF16_WTAP <= CF_WTAP && CF16_WTAP == 3 * 256 * 16, "the workspace holds either image; a weight tile is three loads a thread");
+
 // w [M][9][K] (transposed: w [K][9][M], read as W'[m][tap][k] = w[k][8 - tap][m]) -> ws [M / 64][K / 32][9][3][64][40] bf16.
-// One thread per four k of a row, padding included (zeros)
+// One thread per four k of a row, padding included (zeros).  MF = CF_MF_16: ws [M / 64][K / 32][9][3] planes of cf16_off, no padding
+template <int MF>
 __global__ __launch_bounds__(256) void conv3x3_wsplit_kernel(const float* __restrict__ w, char* __restrict__ ws, int M, int K,
                                                              int transposed, long long total) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int nchunk = K / CF_CK;
-    const int q = (int)(i % 10);
-    long long r = i / 10;
+    constexpr int NQ = MF == CF_MF_32 ? 10 : 8;
+    const int q = (int)(i % NQ);
+    long long r = i / NQ;
     const int co = (int)(r % CF_CO);
     r /= CF_CO;                                          // r = (cot nchunk + chunk) 9 + tap: the tile
     const int tap = (int)(r % 9);
@@ -85,9 +134,15 @@ __global__ __launch_bounds__(256) void conv3x3_wsplit_kernel(const float* __rest
     }
     bf16x4 p[3];
     wrs_split(v, p);
-    char* d = ws + (size_t)r * CF_WTAP + co * CF_PIX + q * 8;
+    if (MF == CF_MF_32) {
+        char* d = ws + (size_t)r * CF_WTAP + co * CF_PIX + q * 8;
 #pragma unroll
-    for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(d + s * CF_WPLANE) = p[s];
+        for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(d + s * CF_WPLANE) = p[s];
+    } else {
+        char* d = ws + (size_t)r * CF16_WTAP + cf16_off(co, q >> 1) + (q & 1) * 8;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(d + s * CF16_WPLANE) = p[s];
+    }
 }
 
 // one operand fragment of v_mfma_f32_32x32x16_bf16: 16 contiguous bytes of a plane in LDS
@@ -116,6 +171,106 @@ __device__ __forceinline__ unsigned cf_sign4(f32x4 r) {             // the mask 
     return (!(r[0] <= 0.f) ? 1u : 0u) | (!(r[1] <= 0.f) ? 2u : 0u) | (!(r[2] <= 0.f) ? 4u : 0u) | (!(r[3] <= 0.f) ? 8u : 0u);
 }
 
+// The way out of the CF_MF_16 main loop (the kernel's comment: EPI, MF).  C layout of the 16 x 16 MFMA: column = lane & 15 (pixel
+// 16 pb + l15 of the wave's row), row = 4 (lane >> 4) + e (channel 16 cb + 4 kg + e): v[cb][pb] is channel quad 4 cb + kg of pixel pb
+template <int EPI>
+__device__ __forceinline__ void cf16_epilogue(const f32x4 (&acc4)[4][2], const f32x4 (&sum4)[4][2], float* ldsf, float* __restrict__ y, int H,
+                                              int W, int Cout, long long n, int r0, int c0, int cot, int tile, int wave, int tid, int l15,
+                                              int kg, const float* __restrict__ bias, uint8_t* __restrict__ mk,
+                                              double* __restrict__ part) {
+    const int row = r0 + wave, c4 = Cout / 4;
+    bool live[2];
+    long long pix[2];                                                // (used where live)
+    f32x4 v[4][2];
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb) {
+        const int col = c0 + 16 * pb + l15;
+        live[pb] = row < H && col < W;
+        pix[pb] = (n * H + row) * W + col;
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) v[cb][pb] = sum4[cb][pb] + acc4[cb][pb];
+    }
+    if (EPI == CF_EPI_RELU || EPI == CF_EPI_POOL) {
+        const f32x4* b4 = reinterpret_cast<const f32x4*>(bias + cot * CF_CO + 4 * kg);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const f32x4 b = b4[4 * cb];
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) v[cb][pb] = cf_relu4(v[cb][pb] + b);
+        }
+    }
+    if (EPI == CF_EPI_MASK) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb) {
+            u32x4 mb = {0u, 0u, 0u, 0u};                             // the 16 sign bytes of this pixel's quads; none past the image: zeros there
+            if (live[pb]) mb = *reinterpret_cast<const u32x4*>(mk + pix[pb] * c4 + cot * (CF_CO / 4));
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const unsigned bits = mb[cb] >> (8 * kg);            // byte 4 cb + kg
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[cb][pb][e] = ((bits >> e) & 1u) != 0u ? v[cb][pb][e] : 0.f;      // (a select, not a product)
+            }
+        }
+    }
+    if (EPI != CF_EPI_POOL) {
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+            if (live[pb]) {
+                float* yp = y + pix[pb] * Cout + cot * CF_CO + 4 * kg;
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) *reinterpret_cast<f32x4*>(yp + 16 * cb) = v[cb][pb];
+            }
+    }
+    if (EPI == CF_EPI_RELU) {
+        if (mk) {                                                    // (the same for every thread of the launch)
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) {
+                unsigned own = 0;                                    // byte cb: quad 4 cb + kg
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) own |= cf_sign4(v[cb][pb]) << (8 * cb);
+                // lane kg of the pixel's four stores the bytes of quads 4 kg ..+3: byte kg of each of the four lanes, in lane order
+                unsigned m4 = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m4 |= ((__shfl(own, l15 + 16 * j) >> (8 * kg)) & 0xffu) << (8 * j);
+                if (live[pb]) *reinterpret_cast<unsigned*>(mk + pix[pb] * c4 + cot * (CF_CO / 4) + 4 * kg) = m4;
+            }
+        }
+    }
+    if (EPI == CF_EPI_POOL) {
+        float* park = ldsf;                                          // every wave is past the last tap's barrier
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb) {
+            float* mine = park + (wave * CF_SW + 16 * pb + l15) * CF_PARK + 4 * kg;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) *reinterpret_cast<f32x4*>(mine + 16 * cb) = v[cb][pb];
+        }
+    }
+    if (EPI == CF_EPI_MASK) {
+        // column sums over the wave's 32 pixels: a lane's two pixels first, then the halving butterfly over its 16-lane group (at
+        // distance d a lane keeps the half of its slots that matches its bit d); slot k = 4 cb + e of the 16 ends in lane l15 = k
+        double s[16];                                                // (fp64 from here to db: see conv3x3_colsum_kernel)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[4 * cb + e] = (double)v[cb][0][e] + (double)v[cb][1][e];
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) {
+            const bool up = (l15 & d) != 0;
+#pragma unroll
+            for (int i = 0; i < d; ++i) {
+                const double send = up ? s[i] : s[i + d], keep = up ? s[i + d] : s[i];
+                s[i] = keep + __shfl_xor(send, d);
+            }
+        }
+        double* red = reinterpret_cast<double*>(ldsf);               // [wave][64 channels]
+        red[wave * CF_CO + 16 * (l15 >> 2) + 4 * kg + (l15 & 3)] = s[0];
+        __syncthreads();
+        if (tid < CF_CO)
+            part[(long long)tile * Cout + cot * CF_CO + tid] = ((red[tid] + red[CF_CO + tid]) + red[2 * CF_CO + tid]) + red[3 * CF_CO + tid];
+    }
+}
+
 // x [N][H][W][Cin], ws as conv3x3_wsplit_kernel leaves it -> y [N][H][W][Cout].  grid xcd_grid(ntiles, Cout / 64), dynamic LDS CF_LDS.
 // tile = ((n nrb + rb) nstrips + strip): rows [4 rb, 4 rb + 4), columns [32 strip, 32 strip + 32)
 //
@@ -133,15 +288,27 @@ __device__ __forceinline__ unsigned cf_sign4(f32x4 r) {             // the mask 
 //                a halving butterfly over the 32 pixels of a wave (31 cross-lane adds a lane, lane l ends with channel slot l), then
 //                the four waves through LDS in wave order
 // bias and mask are read behind the loop: nothing joins the loads its counted waits count
-template <int EPI>
+//
+// MF = CF_MF_16 (dynamic LDS CF16_LDS): a tap is 48 MFMAs of 16 x 16 x 32 - the six products into each of eight accumulators (four
+// 16-channel blocks cb x two 16-pixel blocks pb), product by product, so that an accumulator's next MFMA is eight behind its last and its
+// own order of products is the other shape's - from the same 18 fragment reads (12 weight, 6 pixel).  A lane ends with channels
+// 16 cb + 4 (lane / 16) ..+3 of pixels 16 pb + lane % 16: the sixteen channel quads of a pixel sit in FOUR lanes (16 apart), quad
+// 4 cb + lane / 16 in each, and the epilogues gather accordingly: CF_EPI_RELU transposes the 4 x 4 sign bytes of those lanes (each
+// stores four consecutive bytes a pixel), CF_EPI_POOL parks the same [row][column][channel] tile and leaves by the same code, CF_EPI_MASK
+// adds a lane's two pixels and runs the halving butterfly over 16 lanes (all in fp64, a fixed order: db stays the float next to the
+// exact sum)
+template <int EPI, int MF>
 __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __restrict__ x, const char* __restrict__ ws,
                                                                float* __restrict__ y, int H, int W, int Cin, int Cout, int nstrips,
                                                                int nrb, int ntiles, const float* __restrict__ bias,
                                                                uint8_t* __restrict__ mk, double* __restrict__ part) {
+    constexpr bool M32 = MF == CF_MF_32;
+    constexpr int XPLANE = M32 ? CF_XPLANE : CF16_XPLANE, WTAP = M32 ? CF_WTAP : CF16_WTAP;
     HK_DYN_LDS16(ldsf);
-    char* xs = reinterpret_cast<char*>(ldsf);            // the halo tile of the chunk: [piece][6 x 34 pixels][80 B]
-    char* wb = xs + 3 * CF_XPLANE;                       // two weight tiles: [buf][piece][64 co][80 B]
+    char* xs = reinterpret_cast<char*>(ldsf);            // the halo tile of the chunk: [piece][6 x 34 pixels][80 B] (CF_MF_16: cf16_off)
+    char* wb = xs + 3 * XPLANE;                          // two weight tiles: [buf][piece][64 co][80 B] (CF_MF_16: cf16_off)
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const int l15 = lane & 15, kg = lane >> 4;           // (CF_MF_16: the lane's row or column of a block, and its k-group)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ncot = Cout / CF_CO, nchunk = Cin / CF_CK, total = nchunk * 9;
     int tile, cot;
@@ -151,7 +318,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     const long long n = tr / nrb;
     const int c0 = strip * CF_SW, r0 = rb * CF_R;
     const float* xi = x + n * H * W * Cin;
-    const char* wt = ws + (size_t)cot * total * CF_WTAP + tid * 16;
+    const char* wt = ws + (size_t)cot * total * WTAP + tid * 16;
 
     // this thread's float4 loads of a halo tile: float4 idx -> pixel idx / 8 (row r0 - 1 + pixel / 34, column c0 - 1 + pixel % 34),
     // channels 4 (idx % 8) ..+3 of the chunk; clamped into the image, and whether they count
@@ -167,20 +334,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
         const int rc = row < 0 ? 0 : (row < H ? row : H - 1), cc = col < 0 ? 0 : (col < W ? col : W - 1);
         xoff[u] = ((long long)rc * W + cc) * Cin + 4 * (idx & 7);
     }
-    const int xdst = (tid >> 3) * CF_PIX + (tid & 7) * 8;                      // + 32 u pixels
+    // (CF_MF_16: pixel tid / 8 + 32 u, k-group (tid & 7) / 2, its first or second four k)
+    const int xdst = M32 ? (tid >> 3) * CF_PIX + (tid & 7) * 8 : cf16_off(tid >> 3, (tid & 7) >> 1) + (tid & 1) * 8;      // + 32 u pixels
     const int w3 = tid < 192 ? 3 * 4096 : 0;                                   // the fourth piece of a weight tile: 3072 B, three waves
+    constexpr int NVW = M32 ? 4 : 3;                                           // (CF_MF_16: three whole pieces)
 
-    f32x4 vx[CF_XU], vw[4];
+    f32x4 vx[CF_XU], vw[NVW];
     auto load_x = [&](int chunk) {
         const float* b = xi + chunk * CF_CK;
 #pragma unroll
         for (int u = 0; u < CF_XU; ++u) HK_LOAD16_ASYNC(vx[u], b + xoff[u]);
     };
     auto load_w = [&](int it) {
-        const char* b = wt + (size_t)it * CF_WTAP;
+        const char* b = wt + (size_t)it * WTAP;
 #pragma unroll
         for (int u = 0; u < 3; ++u) HK_LOAD16_ASYNC(vw[u], reinterpret_cast<const float*>(b + 4096 * u));
-        HK_LOAD16_ASYNC(vw[3], reinterpret_cast<const float*>(b + w3));
+        if constexpr (M32) {
+            HK_LOAD16_ASYNC(vw[3], reinterpret_cast<const float*>(b + w3));
+        }
     };
     auto store_x = [&]() {
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -190,28 +361,40 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
                 bf16x4 p[3];
                 wrs_split(((xok >> u) & 1) ? vx[u] : zero, p);
 #pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(xs + s * CF_XPLANE + xdst + u * 32 * CF_PIX) = p[s];
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(xs + s * XPLANE + xdst + u * 32 * (M32 ? CF_PIX : CF16_PIX)) = p[s];
             }
         }
     };
     auto store_w = [&](int buf) {
-        char* d = wb + buf * CF_WTAP + tid * 16;
+        char* d = wb + buf * WTAP + tid * 16;
 #pragma unroll
         for (int u = 0; u < 3; ++u) *reinterpret_cast<f32x4*>(d + 4096 * u) = vw[u];
-        if (tid < 192) *reinterpret_cast<f32x4*>(d + 3 * 4096) = vw[3];
+        if constexpr (M32) {
+            if (tid < 192) *reinterpret_cast<f32x4*>(d + 3 * 4096) = vw[3];
+        }
     };
 
-    f32x16 acc[2], sum[2];
+    f32x16 acc[2], sum[2];                               // CF_MF_32: [channel block of 32]
+    f32x4 acc4[4][2], sum4[4][2];                        // CF_MF_16: [channel block of 16][pixel block of 16]
+    if constexpr (M32) {
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
+        for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[cb][i] = sum[cb][i] = 0.f;
+            for (int i = 0; i < 16; ++i) acc[cb][i] = sum[cb][i] = 0.f;
+    } else {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc4[cb][pb][e] = sum4[cb][pb][e] = 0.f;
+    }
 
     load_w(0);
     load_x(0);
     __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
 #pragma unroll
-    for (int u = 0; u < 4; ++u) HK_PIN_LOADED(vw[u]);
+    for (int u = 0; u < NVW; ++u) HK_PIN_LOADED(vw[u]);
 #pragma unroll
     for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
     store_x();
@@ -230,6 +413,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
             // chunk's x tile: in flight while this tap's MFMAs run
             load_w(it + 1 < total ? it + 1 : it);
             if (tap == 5) load_x(more ? chunk + 1 : chunk);
+            if constexpr (M32) {
             const char* A = wb + (it & 1) * CF_WTAP + aoff;
             const char* B = xs + boff + ((tap / 3) * CF_HW + tap % 3) * CF_PIX;
             bf16x8 a[2][2][3], b[2][3];
@@ -253,11 +437,32 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
                     acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][1], b[ks][0], acc[cb], 0, 0, 0);
                     acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][0], b[ks][0], acc[cb], 0, 0, 0);
                 }
+            } else {
+                // the lane's pixel of this tap, first pixel block; its image offset depends on the pixel (cf16_off)
+                const char* A = wb + (it & 1) * CF16_WTAP + cf16_off(l15, kg);
+                const char* B = xs + cf16_off(wave * CF_HW + l15 + (tap / 3) * CF_HW + tap % 3, kg);
+                bf16x8 a[4][3], b[2][3];
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+#pragma unroll
+                    for (int pb = 0; pb < 2; ++pb) b[pb][s] = cf_frag(B + s * CF16_XPLANE + pb * 16 * CF16_PIX);
+#pragma unroll
+                    for (int cb = 0; cb < 4; ++cb) a[cb][s] = cf_frag(A + s * CF16_WPLANE + cb * 16 * CF16_PIX);
+                }
+                // the same six products in the same order, each into all eight accumulators before the next
+                constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
+#pragma unroll
+                for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+                    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                        for (int pb = 0; pb < 2; ++pb) acc4[cb][pb] = mfma_f32_16x16x32_bf16(a[cb][PA[pr]], b[pb][PB[pr]], acc4[cb][pb]);
+            }
             // the weight loads were issued first: at tap 5 the seven x loads behind them stay in flight until tap 6's wait
             if (tap == 5) __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(CF_XU));
             else __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
 #pragma unroll
-            for (int u = 0; u < 4; ++u) HK_PIN_LOADED(vw[u]);
+            for (int u = 0; u < NVW; ++u) HK_PIN_LOADED(vw[u]);
             if (tap == 6) {
 #pragma unroll
                 for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
@@ -270,14 +475,29 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
             __syncthreads();
         }
         if (++since == CF_FLUSH) {
+            if constexpr (M32) {
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                sum[cb] += acc[cb];
+                for (int cb = 0; cb < 2; ++cb) {
+                    sum[cb] += acc[cb];
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[cb][i] = 0.f;
+                    for (int i = 0; i < 16; ++i) acc[cb][i] = 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                    for (int pb = 0; pb < 2; ++pb) {
+                        sum4[cb][pb] += acc4[cb][pb];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc4[cb][pb][e] = 0.f;
+                    }
             }
             since = 0;
         }
+    }
+    if constexpr (!M32) {
+        cf16_epilogue<EPI>(acc4, sum4, ldsf, y, H, W, Cout, n, r0, c0, cot, tile, wave, tid, l15, kg, bias, mk, part);
+        if (EPI != CF_EPI_POOL) return;                  // (the pooled tile is parked: it leaves below, as the other shape's)
     }
     // C layout of the 32 x 32 MFMA: column = lane & 31 (pixel), row = 8 (i / 4) + 4 (lane >> 5) + i % 4 (output channel)
     const int row = r0 + wave, col = c0 + l31;
@@ -301,13 +521,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     const long long pix = (n * H + row) * W + col;                  // (used where live)
     const int c4 = Cout / 4;
     f32x4 v[2][4];
+    if constexpr (M32) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[cb][j][e] = sum[cb][4 * j + e] + acc[cb][4 * j + e];
-    if (EPI == CF_EPI_RELU || EPI == CF_EPI_POOL) {
+    }
+    if (M32 && (EPI == CF_EPI_RELU || EPI == CF_EPI_POOL)) {
         const f32x4* b4 = reinterpret_cast<const f32x4*>(bias + cot * CF_CO + 4 * hf);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
@@ -342,11 +564,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     }
     if (EPI == CF_EPI_POOL) {
         float* park = ldsf;                                          // [4 rows][32 columns][CF_PARK floats]: every wave is past the last tap's barrier
+        if constexpr (M32) {
         float* mine = park + (wave * CF_SW + l31) * CF_PARK + 4 * hf;
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(mine + cb * 32 + 8 * j) = v[cb][j];
+        }                                                            // (CF_MF_16: cf16_epilogue has parked the same tile)
         __syncthreads();
         const int q = tid & 15, pc = tid >> 4;                       // channel quad, pooled column of the tile; pooled rows u = 0, 1
         const int Ho = H / 2, Wo = W / 2;
@@ -457,21 +681,29 @@ __global__ __launch_bounds__(64 * Q) void conv3x3_colsum_kernel(const double* __
 }
 
 // x [N][H][W][K] (*) w -> y [N][H][W][M] (or what EPI makes of it): the pre-pass and the main kernel; M, K multiples of 64
-template <int EPI>
-static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
-                       hipStream_t stream, const float* bias = nullptr, uint8_t* mk = nullptr, double* part = nullptr) {
+template <int EPI, int MF>
+static int conv3x3_run_on(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
+                          hipStream_t stream, const float* bias, uint8_t* mk, double* part) {
+    constexpr int LDS = MF == CF_MF_32 ? CF_LDS : CF16_LDS;
     const long long nstrips = ((long long)W + CF_SW - 1) / CF_SW, nrb = ((long long)H + CF_R - 1) / CF_R, ntiles = N * nrb * nstrips;
     const int ncot = M / CF_CO;
     if ((ntiles + NXCD) * ncot > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
-    const long long total = (long long)ncot * (K / CF_CK) * 9 * CF_CO * 10;
-    hipLaunchKernelGGL(conv3x3_wsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (char*)ws, M, K,
+    const long long total = (long long)ncot * (K / CF_CK) * 9 * CF_CO * (MF == CF_MF_32 ? 10 : 8);
+    hipLaunchKernelGGL(conv3x3_wsplit_kernel<MF>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (char*)ws, M, K,
                        transposed ? 1 : 0, total);
     HK_LAUNCH_CHECK();
-    HK_ALLOW_BIG_LDS(conv3x3_split_kernel<EPI>, CF_LDS);
-    hipLaunchKernelGGL(conv3x3_split_kernel<EPI>, dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), CF_LDS, stream, x, (const char*)ws,
+    HK_ALLOW_BIG_LDS((conv3x3_split_kernel<EPI, MF>), LDS);
+    hipLaunchKernelGGL((conv3x3_split_kernel<EPI, MF>), dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), LDS, stream, x, (const char*)ws,
                        y, H, W, K, M, (int)nstrips, (int)nrb, (int)ntiles, bias, mk, part);
     HK_LAUNCH_CHECK();
     return HK_OK;
+}
+// ... on the MFMA shape the knob `conv_mfma` names: 1 = 16 x 16 x 32, anything else = 32 x 32 x 16
+template <int EPI>
+static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
+                       hipStream_t stream, const float* bias = nullptr, uint8_t* mk = nullptr, double* part = nullptr) {
+    if (tuning().conv_mfma == 1) return conv3x3_run_on<EPI, CF_MF_16>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part);
+    return conv3x3_run_on<EPI, CF_MF_32>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part);
 }
 
 static int conv3x3_check(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,

@@ -6,6 +6,7 @@ Outputs and workspaces are allocated through torch's caching allocator; kernels
 are enqueued on torch's current HIP stream; nothing synchronises the host.
 fp32 only, HIP tensors only - there is no CPU fallback (see hawkeye_amd/_lib.py).
 """
+import contextlib
 import threading
 
 import numpy as np
@@ -1988,6 +1989,44 @@ def conv3x3_bwd_data_ok(x, conv):
             and conv3x3_bwd_data_route(conv.in_channels, conv.out_channels, x.shape[0], x.shape[2], x.shape[3]))
 
 
+# The layers whose forward / input gradient runs conv3x3_split_kernel on v_mfma_f32_16x16x32_bf16 instead of v_mfma_f32_32x32x16_bf16
+# by default (knob `conv_mfma` at -1): (Cin, Cout, H, W) -> the batch sizes at which EVERY layer of that shape cleared the stand-alone
+# bar (profiles/conv_mfma_timing.json: the 32 x 32 x 16 arm's fastest repeat minus the 16 x 16 x 32 arm's slowest more than three times
+# the 32 x 32 x 16 arm's own spread) AND was faster inside the training step (profiles/conv_mfma_step_layers.json; DESIGN 3.10, "The
+# MFMA shape").  Nothing that was not measured is here; a shape or batch that is not listed keeps 32 x 32 x 16.
+CONV_MFMA16_FWD = {
+    (256, 256, 112, 112): (64,),                                                                       # conv3_2 / conv3_3
+    (256, 512, 56, 56): (64, 16), (512, 512, 56, 56): (64,),                                           # conv4_1, conv4_2 / conv4_3
+    (512, 512, 28, 28): (16,),                                                                         # conv5_1 / conv5_2 / conv5_3
+}
+CONV_MFMA16_BWD_DATA = {
+    (64, 64, 448, 448): (64,),                                                                         # conv1_2
+    (128, 256, 112, 112): (64, 16), (256, 256, 112, 112): (64, 16),                                    # conv3_1, conv3_2 / conv3_3
+    (256, 512, 56, 56): (64, 16), (512, 512, 56, 56): (64, 16),                                        # conv4_1, conv4_2 / conv4_3
+    (512, 512, 28, 28): (16,),                                                                         # conv5_1 / conv5_2 / conv5_3
+}
+
+
+def conv3x3_mfma_route(direction, cin, cout, n, h, w):
+    """Whether the forward (`direction` 'fwd') or the input gradient ('bwd_data') of the layer (Cin, Cout) on N maps of H x W runs on the
+    16 x 16 x 32 bf16 MFMA: knob `conv_mfma` at 1 every call, at 0 none, at -1 (default) the layers of CONV_MFMA16_FWD /
+    CONV_MFMA16_BWD_DATA at their measured batch sizes."""
+    v = _knob(b'conv_mfma')
+    if v >= 0:
+        return v == 1
+    table = CONV_MFMA16_FWD if direction == 'fwd' else CONV_MFMA16_BWD_DATA
+    return n in table.get((cin, cout, h, w), ())
+
+
+def _conv3x3_mfma(direction, cin, cout, n, h, w):
+    """The scope of one entry-point call of csrc/conv_fwd.hip: with the knob at its default the table's choice reaches the library as
+    the knob's value for the length of the call (the entry points' signatures carry no shape of the instruction); a forced knob is
+    left alone."""
+    if _knob(b'conv_mfma') < 0 and conv3x3_mfma_route(direction, cin, cout, n, h, w):
+        return _lib.tuning(conv_mfma=1)
+    return contextlib.nullcontext()
+
+
 def _conv3x3_call(fn, what, src, weight, cout_of_result):
     lib = _lib.load()
     _nhwc(src, what)
@@ -2003,7 +2042,8 @@ def _conv3x3_call(fn, what, src, weight, cout_of_result):
     out = torch.empty((n, cout if cout_of_result else cin, h, w), dtype=torch.float32, device=src.device, memory_format=torch.channels_last)
     nws = lib.hk_conv3x3_ws_bytes(cin, cout)
     ws = _ws(nws, src.device)
-    check(getattr(lib, fn)(psrc, pw, ptr(out), n, h, w, cin, cout, ptr(ws), nws, stream()), fn)
+    with _conv3x3_mfma('fwd' if cout_of_result else 'bwd_data', cin, cout, n, h, w):
+        check(getattr(lib, fn)(psrc, pw, ptr(out), n, h, w, cin, cout, ptr(ws), nws, stream()), fn)
     return out
 
 
@@ -2136,13 +2176,15 @@ class _ConvUnit(torch.autograd.Function):
         if pool:
             y = torch.empty((n, cout, h // 2, w // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
             aux = torch.empty(n, h // 2, w // 2, cout // 4, dtype=torch.uint8, device=x.device)
-            check(lib.hk_conv3x3_bias_relu_pool_fwd(px, pw, ptr(b), ptr(y), ptr(aux), n, h, w, cin, cout, ptr(ws), nws, stream()),
-                  'hk_conv3x3_bias_relu_pool_fwd')
+            with _conv3x3_mfma('fwd', cin, cout, n, h, w):
+                check(lib.hk_conv3x3_bias_relu_pool_fwd(px, pw, ptr(b), ptr(y), ptr(aux), n, h, w, cin, cout, ptr(ws), nws, stream()),
+                      'hk_conv3x3_bias_relu_pool_fwd')
         else:
             y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
             aux = torch.empty(n, h, w, cout // 4, dtype=torch.uint8, device=x.device) if grad else None
-            check(lib.hk_conv3x3_bias_relu_fwd(px, pw, ptr(b), ptr(y), ptr(aux), n, h, w, cin, cout, ptr(ws), nws, stream()),
-                  'hk_conv3x3_bias_relu_fwd')
+            with _conv3x3_mfma('fwd', cin, cout, n, h, w):
+                check(lib.hk_conv3x3_bias_relu_fwd(px, pw, ptr(b), ptr(y), ptr(aux), n, h, w, cin, cout, ptr(ws), nws, stream()),
+                      'hk_conv3x3_bias_relu_fwd')
             link_out.mask = aux
         min_ = link_in.mask if (masked and link_in is not None) else None
         ctx.save_for_backward(x, weight, aux, y if pool else None, min_)
@@ -2185,8 +2227,9 @@ class _ConvUnit(torch.autograd.Function):
                 dbp = torch.empty(cin, dtype=torch.float32, device=x.device)
                 nws = lib.hk_conv3x3_masked_ws_bytes(n, h, w, cin, cout)
                 ws = _ws(nws, x.device)
-                check(lib.hk_conv3x3_masked_bwd_data(ptr(g), ptr(weight), ptr(min_), ptr(dx), ptr(dbp), n, h, w, cin, cout, ptr(ws), nws,
-                                                     stream()), 'hk_conv3x3_masked_bwd_data')
+                with _conv3x3_mfma('bwd_data', cin, cout, n, h, w):
+                    check(lib.hk_conv3x3_masked_bwd_data(ptr(g), ptr(weight), ptr(min_), ptr(dx), ptr(dbp), n, h, w, cin, cout, ptr(ws), nws,
+                                                         stream()), 'hk_conv3x3_masked_bwd_data')
                 link_in.db = dbp
             else:
                 dx = conv3x3_bwd_data_raw(g, weight)

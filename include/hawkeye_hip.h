@@ -77,6 +77,9 @@ const char* hk_version(void);
  *   "conv_bwd_data" the same for the input gradient of those convolutions
  *   "conv_epi"      epilogues inside those kernels: 2 (default) = bias + ReLU (+ pool) in the forward and the producing layer's ReLU
  *                   mask + bias-gradient partials in the input gradient, 1 = the forward ones only, 0 = none (separate passes)
+ *   "conv_mfma"     the bf16 MFMA those kernels run on: 1 = v_mfma_f32_16x16x32_bf16, 0 = v_mfma_f32_32x32x16_bf16, -1 (default) = per
+ *                   call: 32x32x16 unless the caller has set 1 for the call, as the Python layer does for the layers of its
+ *                   measured table.  Same results to the bound of hawkeye_conv.h either way; the bits differ
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
