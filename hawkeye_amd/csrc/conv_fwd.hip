@@ -8,7 +8,7 @@
 //
 //   pre-pass = conv3x3_wsplit_kernel splits the weights (hk_split_bf16.h) once per call and writes them in the order the main kernel
 //              stages them: [Cout tile of 64][Cin chunk of 32][tap][piece hi, mid, lo][64 co][40 bf16] - the 32 channels of a row and
-//              8 of padding, the LDS image itself, so that staging is a 16-byte copy per thread and load.  `transposed` reads W'
+//              8 of padding, the LDS image itself, so that staging is a 16-byte LDS-DMA per lane and piece.  `transposed` reads W'
 //              out of W.  Not cached across calls: the weights change every step
 //   tile     = a workgroup (four waves) owns 64 output channels x 4 rows x 32 columns of one image; wave r owns row r: two 32 x 32
 //              MFMA blocks (co 0 - 31, 32 - 63) x 32 pixels.  The weights are the operand whose index is the accumulator ROW, so a
@@ -20,9 +20,15 @@
 //   x        = per Cin chunk of 32 the halo tile, 6 rows x 34 columns, is split on its way from registers to LDS (once per element
 //              and workgroup) and used by all nine taps: a tap is an address offset.  Rows and columns outside the image and past a
 //              ragged edge are zeros in LDS; the load itself is made from a clamped, in-bounds address, never skipped
-//   pipeline = the weight tile of a (chunk, tap) is double-buffered (2 x 15360 B): tap t + 1 comes in through registers while the
-//              MFMAs of tap t run; the next chunk's x tile is requested at tap 5 and stored behind tap 8; one barrier per tap
-//              (24 MFMAs per wave), two at a chunk's end
+//   pipeline = the weight tile of a (chunk, tap) is double-buffered (2 x 15360 B): tap t + 1 comes in by LDS-DMA (glds16: the
+//              workspace is the LDS image, a wave's three or four pieces are 1 KiB each in both; no register, no ds_write) while
+//              the MFMAs of tap t run.  A tap reads its 18 fragments, runs its MFMAs and ends with CF_TAP_BARRIER: a counted
+//              s_waitcnt vmcnt(n) lgkmcnt(0) and a raw s_barrier - never __syncthreads(), whose fence would drain every request in
+//              flight.  The next chunk's x tile is requested at tap 5 behind the weight pieces (vmcnt(7) there: it stays in flight
+//              until tap 6's wait) and stored behind tap 8; one barrier per tap (24 MFMAs per wave), two at a chunk's end.
+//              Measured against staging through registers + ds_write_b128 ("Weight tiles by LDS-DMA"): the step
+//              3.2 ms of 112 faster at batch 64, every output of every instantiation bit-identical.  A third buffer (CF_MF_16:
+//              76032 B, the tile two taps ahead, vmcnt(3)) measured 0.1 ms: inside the spread, not kept
 //   chains   = the bf16 MFMA does not round its running sum as an fp32 fma does (conv_wrw.hip: "chains"): every CF_FLUSH = 3 chunks
 //              (K = 864) the accumulators are added to a second fp32 set with ordinary additions and start again from zero
 //              (one chain of 4608 at Cin = 512, measured on a build without the restart: 2.3 - 8.3e-7 S from float64, inside the 1.5e-6
@@ -45,7 +51,8 @@
 //              every pixel offset, 63744 B).  Measured at batch 64 ("The MFMA shape"): 196 - 227 TF/s stand-alone where the
 //              other shape gives 177 - 205; in the step the 24 launches 70.2 ms against 80.2 with every layer on it; per launch 9 - 11 %
 //              fewer cycles (LDS bank conflicts 7 % -> 0, a fifth less weight traffic) at a 3 - 4 % higher clock, the matrix pipe
-//              61 - 72 % busy.  Routed per layer, direction and batch by functional.py's measured table; MF = 0 is the code as it was
+//              61 - 72 % busy.  Routed per layer, direction and batch by functional.py's measured table.  Registers
+//              with the weight tiles by DMA and every fragment read in front of the MFMAs: 204 - 206 VGPRs (MF = 0: 190 - 192), no spill
 #include "hk_common.h"
 #include "hk_split_bf16.h"
 #include <hk_mfma_bf16.h>   // the 16 x 16 x 32 bf16 MFMA (the emulation build finds its model of it first)
@@ -78,6 +85,16 @@ constexpr int CF16_XPLANE = CF_HPIX * CF16_PIX;          // 13056 B
 constexpr int CF16_WPLANE = CF_CO * CF16_PIX;            // 4096 B
 constexpr int CF16_WTAP = 3 * CF16_WPLANE;               // 12288 B: three 16-byte loads a thread
 constexpr int CF16_LDS = 3 * CF16_XPLANE + 2 * CF16_WTAP;  // 63744 B
+// The barrier that ends a tap: s_waitcnt vmcnt(n) lgkmcnt(0) + s_barrier.  HK_VM_BARRIER(n) with the LDS reads waited for as well: the
+// DMA that another wave issues behind this barrier goes into the buffer this tap read, so no fragment read may still be on its way
+// (the reads are issued in front of the MFMAs: the wait finds them done), and no __syncthreads(), whose fence drains vmcnt(0)
+#define CF_TAP_BARRIER(n)                                                                                      \
+    do {                                                                                                       \
+        asm volatile("" ::: "memory");                 /* no LDS access moves across */                        \
+        __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(n) & ~(15 << 8));                                              \
+        __builtin_amdgcn_s_barrier();                                                                          \
+        asm volatile("" ::: "memory");                                                                         \
+    } while (0)
 // THE image of a CF_MF_16 plane, for the staging stores, the fragment reads and the weight pre-pass: byte offset of k-group kg
 // (eight k, 16 bytes) of row `row` (a pixel of the halo tile, or a weight row).  The 80-byte pitch of the other shape puts rows 1
 // and 4 of a ds_read_b128 lane group on one slot; no plain pitch separates the groups, and on the 80-byte pitch no XOR of period 16
@@ -336,21 +353,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     }
     // (CF_MF_16: pixel tid / 8 + 32 u, k-group (tid & 7) / 2, its first or second four k)
     const int xdst = M32 ? (tid >> 3) * CF_PIX + (tid & 7) * 8 : cf16_off(tid >> 3, (tid & 7) >> 1) + (tid & 1) * 8;      // + 32 u pixels
-    const int w3 = tid < 192 ? 3 * 4096 : 0;                                   // the fourth piece of a weight tile: 3072 B, three waves
-    constexpr int NVW = M32 ? 4 : 3;                                           // (CF_MF_16: three whole pieces)
 
-    f32x4 vx[CF_XU], vw[NVW];
+    f32x4 vx[CF_XU];
     auto load_x = [&](int chunk) {
         const float* b = xi + chunk * CF_CK;
 #pragma unroll
         for (int u = 0; u < CF_XU; ++u) HK_LOAD16_ASYNC(vx[u], b + xoff[u]);
     };
-    auto load_w = [&](int it) {
+    // tile `it` on its way into buffer `buf` by LDS-DMA, no register in between: the workspace IS the LDS image, and a wave's 64 lanes
+    // x 16 bytes are 1 KiB contiguous in both - what one glds16 copies (LDS base wave-uniform, lane l lands at + 16 l).  CF_MF_32: the
+    // fourth piece is 3072 B - waves 0 - 2 (wave 3 has one operation fewer in flight: the counted waits count from the youngest)
+    auto load_w = [&](int it, int buf) {
         const char* b = wt + (size_t)it * WTAP;
+        char* d = wb + buf * WTAP + wave * 1024;
 #pragma unroll
-        for (int u = 0; u < 3; ++u) HK_LOAD16_ASYNC(vw[u], reinterpret_cast<const float*>(b + 4096 * u));
+        for (int u = 0; u < 3; ++u) glds16(reinterpret_cast<const float*>(b + 4096 * u), reinterpret_cast<float*>(d + 4096 * u));
         if constexpr (M32) {
-            HK_LOAD16_ASYNC(vw[3], reinterpret_cast<const float*>(b + w3));
+            if (wave < 3) glds16(reinterpret_cast<const float*>(b + 3 * 4096), reinterpret_cast<float*>(d + 3 * 4096));
         }
     };
     auto store_x = [&]() {
@@ -363,14 +382,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
 #pragma unroll
                 for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(xs + s * XPLANE + xdst + u * 32 * (M32 ? CF_PIX : CF16_PIX)) = p[s];
             }
-        }
-    };
-    auto store_w = [&](int buf) {
-        char* d = wb + buf * WTAP + tid * 16;
-#pragma unroll
-        for (int u = 0; u < 3; ++u) *reinterpret_cast<f32x4*>(d + 4096 * u) = vw[u];
-        if constexpr (M32) {
-            if (tid < 192) *reinterpret_cast<f32x4*>(d + 3 * 4096) = vw[3];
         }
     };
 
@@ -390,16 +401,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
                 for (int e = 0; e < 4; ++e) acc4[cb][pb][e] = sum4[cb][pb][e] = 0.f;
     }
 
-    load_w(0);
+    load_w(0, 0);
     load_x(0);
-    __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
-#pragma unroll
-    for (int u = 0; u < NVW; ++u) HK_PIN_LOADED(vw[u]);
+    __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));         // (this wave's pieces of tile 0 have landed, too)
 #pragma unroll
     for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
     store_x();
-    store_w(0);
-    __syncthreads();
+    HK_LDS_BARRIER();
 
     const int aoff = l31 * CF_PIX + hf * 16;                        // this lane's weight row (+ 32 rows for the second block)
     const int boff = (wave * CF_HW + l31) * CF_PIX + hf * 16;       // this lane's pixel at tap (0, 0)
@@ -409,9 +417,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int it = chunk * 9 + tap;
-            // the next weight tile (the last step loads its own again: an unconditional, in-bounds load) and, at tap 5, the next
-            // chunk's x tile: in flight while this tap's MFMAs run
-            load_w(it + 1 < total ? it + 1 : it);
+            // the next weight tile (the last step requests its own again: an unconditional, in-bounds request) into the buffer tap - 1
+            // read - every wave is past the barrier that ended that tap, with its reads done - and, at tap 5, the next chunk's x tile:
+            // in flight while this tap's MFMAs run
+            load_w(it + 1 < total ? it + 1 : it, (it + 1) & 1);
             if (tap == 5) load_x(more ? chunk + 1 : chunk);
             if constexpr (M32) {
             const char* A = wb + (it & 1) * CF_WTAP + aoff;
@@ -425,6 +434,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
                     a[ks][0][s] = cf_frag(A + s * CF_WPLANE + ks * 32);
                     a[ks][1][s] = cf_frag(A + s * CF_WPLANE + 32 * CF_PIX + ks * 32);
                 }
+            __builtin_amdgcn_sched_barrier(0);           // every fragment read in front of the MFMAs (CF_TAP_BARRIER)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -449,6 +459,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
 #pragma unroll
                     for (int cb = 0; cb < 4; ++cb) a[cb][s] = cf_frag(A + s * CF16_WPLANE + cb * 16 * CF16_PIX);
                 }
+                __builtin_amdgcn_sched_barrier(0);       // every fragment read in front of the MFMAs (CF_TAP_BARRIER)
                 // the same six products in the same order, each into all eight accumulators before the next
                 constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
 #pragma unroll
@@ -458,21 +469,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
 #pragma unroll
                         for (int pb = 0; pb < 2; ++pb) acc4[cb][pb] = mfma_f32_16x16x32_bf16(a[cb][PA[pr]], b[pb][PB[pr]], acc4[cb][pb]);
             }
-            // the weight loads were issued first: at tap 5 the seven x loads behind them stay in flight until tap 6's wait
-            if (tap == 5) __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(CF_XU));
-            else __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
-#pragma unroll
-            for (int u = 0; u < NVW; ++u) HK_PIN_LOADED(vw[u]);
+            // The tap ends with a counted wait and a raw barrier: tile it + 1 has landed for every wave, and every wave has read this
+            // tap's buffer.  Requests retire in order and the weight pieces were issued first: at tap 5 the seven x loads behind them
+            // stay in flight, and tap 6's wait - its own pieces are behind them - covers them
+            if (tap == 5) CF_TAP_BARRIER(CF_XU);
+            else CF_TAP_BARRIER(0);                      // (tap 8: and every wave is past its last read of the chunk's x tile)
             if (tap == 6) {
 #pragma unroll
                 for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
             }
-            store_w((it + 1) & 1);                       // the buffer tap - 1 read: a barrier ago
             if (tap == 8 && more) {
-                __syncthreads();                         // every wave is past its last read of the chunk's x tile
                 store_x();
+                HK_LDS_BARRIER();                        // (lgkmcnt(0): the x tile's writes have landed)
             }
-            __syncthreads();
         }
         if (++since == CF_FLUSH) {
             if constexpr (M32) {
