@@ -71,9 +71,24 @@
 //              (profiles/wrw_wide_timing.json, rows `split_slices_adjacent`: within the repeats' spread on all twenty rows)
 //   measured = 190 - 217 TF/s stand-alone at batch 64 where the library's fp32 kernels give 125 - 131, 26.8 ms for the ten layers in
 //              the training step against the library's 48.5
+//
+// MFMA (template parameter MF, knob wrw_mfma): the split form on v_mfma_f32_16x16x32_bf16 (WRS_MF_16) beside v_mfma_f32_32x32x16_bf16
+// (WRS_MF_32, the code above, instruction for instruction what it was).  Same wave tile (32 output x 32 input channels x 9 taps), same jobs,
+// ring, borders, flush, partial results and order of the six products; per tap 2 x 2 blocks of 16 x 16, 36 f32x4 accumulators (the same
+// 144 registers), one MFMA over the strip row's 32 pixels, 24 MFMAs of 16 cycles per (row, tap) = the 384 pipe cycles of two rounds above.
+//   image    = planes [piece][16-channel quarter][35 pixels][16 channels], 32 B a pixel (wrs16_off), k permuted so that a 16-lane group
+//              reads four consecutive pixels per transposing read (wrs16_kpix): reads and stores conflict-free, static_asserted there
+//   limits   = 244 registers, no scratch, no spill, LDS 6 x 13440 = 80640 B (dynamic): two workgroups per CU (kernel-resource-usage)
+//   measured = the same cycles (conv1_2: 7.79 M against 7.64 M, the matrix pipe 71 % busy either way) at a higher clock (1.69 against
+//              1.55 GHz; conv4_2 1.79 against 1.66): every one of the twelve layers 1 - 4 % faster inside the training step at batch 64
+//              and none slower at 16, 34.3 -> 33.1 ms per step for the twelve (profiles/wrw_mfma_step_layers.json), the step 108.9 ->
+//              107.5 ms.  The rule behind the knob's default is therefore "always" (wrw_mfma16_wins).  The split and
+//              the LDS stores moved in between the MFMAs (no serial tail) took 2.6 % of the cycles and gave most of it back in clock:
+//              0.7 ms of the step, inside the bar - not kept
 #include "hk_common.h"
 #include "hk_partial_sum.h"
 #include "hk_split_bf16.h"
+#include <hk_mfma_bf16.h>   // the 16 x 16 x 32 bf16 MFMA (the emulation build finds its model of it first)
 #include "../../include/hawkeye_hip.h"
 
 namespace hk {
@@ -249,27 +264,28 @@ constexpr int WRS_LDS = 4 * WRS_XSLOT + 2 * WRS_DBUF;    // 76800 B: two workgro
 constexpr int WRS_FLUSH = 32;                            // row steps (1024 pixels) an accumulator chain runs before it is added to the partial
 
 // float4 idx of a row segment (pixel idx / 16, channels 4 (idx % 16) ..+3) -> the three pieces, 8 bytes each, at
-// [piece][channel half = (idx % 16) / 8][pixel][4 (idx % 8)] of the planes at `base` (plane = bytes of one plane)
-__device__ __forceinline__ void wrs_store(char* base, int plane, f32x4 v) {
+// [piece][channel half = (idx % 16) / 8][pixel][4 (idx % 8)] of the planes at `base` (piece = bytes from one piece to the next; WRS_MF_16:
+// the image of wrs16_off, below)
+__device__ __forceinline__ void wrs_store(char* base, int piece, f32x4 v) {
     bf16x4 p[3];
     wrs_split(v, p);
 #pragma unroll
-    for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(base + 2 * s * plane) = p[s];
+    for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(base + s * piece) = p[s];
 }
 __device__ __forceinline__ void wrs_store_x(char* xs, int slot, const WrwStage& st, bool rok, const f32x4 (&v)[3]) {
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int tid = threadIdx.x;
     char* d = xs + slot * WRS_XSLOT + ((tid >> 3) & 1) * WRS_XPLANE + (tid >> 4) * WRS_PIX + (tid & 7) * 8;
-    wrs_store(d, WRS_XPLANE, (rok && st.xok[0]) ? v[0] : zero);
-    wrs_store(d + 16 * WRS_PIX, WRS_XPLANE, (rok && st.xok[1]) ? v[1] : zero);
-    if (tid + 512 < WRW_XF4) wrs_store(d + 32 * WRS_PIX, WRS_XPLANE, (rok && st.xok[2]) ? v[2] : zero);
+    wrs_store(d, 2 * WRS_XPLANE, (rok && st.xok[0]) ? v[0] : zero);
+    wrs_store(d + 16 * WRS_PIX, 2 * WRS_XPLANE, (rok && st.xok[1]) ? v[1] : zero);
+    if (tid + 512 < WRW_XF4) wrs_store(d + 32 * WRS_PIX, 2 * WRS_XPLANE, (rok && st.xok[2]) ? v[2] : zero);
 }
 __device__ __forceinline__ void wrs_store_dy(char* ds, int buf, const WrwStage& st, const f32x4 (&v)[2]) {
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int tid = threadIdx.x;
     char* d = ds + buf * WRS_DBUF + ((tid >> 3) & 1) * WRS_DPLANE + (tid >> 4) * WRS_PIX + (tid & 7) * 8;
-    wrs_store(d, WRS_DPLANE, st.dok[0] ? v[0] : zero);
-    wrs_store(d + 16 * WRS_PIX, WRS_DPLANE, st.dok[1] ? v[1] : zero);
+    wrs_store(d, 2 * WRS_DPLANE, st.dok[0] ? v[0] : zero);
+    wrs_store(d + 16 * WRS_PIX, 2 * WRS_DPLANE, st.dok[1] ? v[1] : zero);
 }
 // One operand fragment of v_mfma_f32_32x32x16_bf16: the eight pixels blk .. blk + 7 of this lane's channel.  `blk` = the plane's
 // bytes at (first pixel + 8 (lane / 32), channel 16 ((lane / 16) % 2)): the 4 pixel x 16 channel block of the lane's 16-lane group;
@@ -315,16 +331,161 @@ __device__ __forceinline__ void wrs_flush(float* __restrict__ pb, f32x16 (&acc)[
     }
 }
 
+// ---- MF, the bf16 MFMA the split form runs on (knob wrw_mfma; header: "MFMA") ----
+// WRS_MF_32 = v_mfma_f32_32x32x16_bf16 on the planes above, WRS_MF_16 = v_mfma_f32_16x16x32_bf16 on the image below.
+constexpr int WRS_MF_32 = 0, WRS_MF_16 = 1;
+constexpr int WRS16_PIX = 16 * 2;                        // bytes of a pixel in a plane: 16 channels, bf16
+constexpr int WRS16_PITCH = WRW_SW + 3;                  // pixels of a plane: the 34 of an x row segment + 1 (dy uses 32), "banks" below
+constexpr int WRS16_QPLANE = WRS16_PITCH * WRS16_PIX;    // 1120 B: [35 pixels][16 channels] of one piece, one 16-channel quarter
+constexpr int WRS16_PIECE = 4 * WRS16_QPLANE;            // 4480 B
+constexpr int WRS16_SLOT = 3 * WRS16_PIECE;              // 13440 B: an x ring slot and a dy buffer alike
+constexpr int WRS16_LDS = 6 * WRS16_SLOT;                // 80640 B: two workgroups per CU in 160 KB
+
+// THE image of a WRS_MF_16 row segment, for the staging stores, the fragment reads and the host twin of the reads: byte offset of
+// channel `ch` (0 .. 15) of quarter `quarter` at pixel `pixel` in piece `piece`
+__host__ __device__ constexpr int wrs16_off(int piece, int quarter, int pixel, int ch) {
+    return piece * WRS16_PIECE + quarter * WRS16_QPLANE + pixel * WRS16_PIX + ch * 2;
+}
+// THE order of the GEMM's k inside a 16 x 16 x 32 MFMA: element e (0 .. 7) of the fragment of 16-lane group g is this pixel of the
+// strip row (+ kw for x).  The instruction sums over all 32, and dy and x use the same order, so any permutation serves; this one
+// gives a group four consecutive pixels per transposing read and a 32-lane half eight: 256 contiguous bytes of one plane
+__host__ __device__ constexpr int wrs16_kpix(int g, int e) { return 16 * (e >> 2) + 4 * g + (e & 3); }
+//   banks    = ds_read_b64_tr_b16 is serviced in two halves of 32 lanes, bank = (a / 4) % 64: a half's two groups read pixels
+//              8 h ..+7 (+ 16 in the second read, + kw) of one quarter plane, 256 contiguous bytes from a multiple of 32 - every bank
+//              once, at any kw and any plane pitch.  ds_write_b64 is serviced in four groups of 16 lanes, bank = (a / 4) % 32: a
+//              group's lanes store one pixel's four quarters, 32 bytes each; with 35 pixels (280 dwords) to a plane the quarters
+//              start 24 banks apart - 0, 24, 16, 8 - and the group covers the 32 banks once (with 34 pixels quarters 0 and 2
+//              would meet: 2-way, what the WRS_MF_32 image's stores have always had).  Both static_asserted:
+constexpr bool wrs16_reads_conflict_free() {
+    for (int piece = 0; piece < 3; ++piece)
+        for (int quarter = 0; quarter < 4; ++quarter)
+            for (int kw = 0; kw < 3; ++kw)
+                for (int rd = 0; rd < 2; ++rd)
+                    for (int half = 0; half < 2; ++half) {
+                        unsigned long long seen = 0;
+                        for (int l = 32 * half; l < 32 * half + 32; ++l) {
+                            const int g = l >> 4, i = l & 15;
+                            const int a = wrs16_off(piece, quarter, kw + wrs16_kpix(g, 4 * rd) + (i >> 2), 4 * (i & 3));
+                            if (a % 8 != 0 || kw + wrs16_kpix(g, 4 * rd + 3) >= WRS16_PITCH) return false;
+                            for (int d = 0; d < 2; ++d) {
+                                const int bank = (a / 4 + d) % 64;
+                                if ((seen >> bank) & 1ull) return false;
+                                seen |= 1ull << bank;
+                            }
+                        }
+                    }
+    return true;
+}
+constexpr bool wrs16_stores_conflict_free() {
+    for (int u = 0; u < 3; ++u)                          // a thread's float4 idx = tid + 256 u of a row segment: pixel idx / 16, quarter (idx / 4) % 4
+        for (int grp = 0; grp < 16; ++grp) {
+            unsigned seen = 0;
+            for (int tid = 16 * grp; tid < 16 * grp + 16; ++tid) {
+                const int a = wrs16_off(0, (tid >> 2) & 3, (tid >> 4) + 16 * u, 4 * (tid & 3));
+                for (int d = 0; d < 2; ++d) {
+                    const int bank = (a / 4 + d) % 32;
+                    if ((seen >> bank) & 1u) return false;
+                    seen |= 1u << bank;
+                }
+            }
+        }
+    return true;
+}
+constexpr bool wrs16_k_is_a_permutation() {
+    unsigned seen = 0;
+    for (int g = 0; g < 4; ++g)
+        for (int e = 0; e < 8; ++e) seen |= 1u << wrs16_kpix(g, e);
+    return seen == 0xffffffffu;
+}
+static_assert(wrs16_reads_conflict_free(), "both 32-lane halves of both transposing reads of a WRS_MF_16 fragment cover the 64 banks once, at every kw");
+static_assert(wrs16_stores_conflict_free(), "every 16-lane group of a WRS_MF_16 staging store covers the 32 banks once");
+static_assert(wrs16_k_is_a_permutation(), "the four groups' fragments hold the strip row's 32 pixels once each");
+static_assert(2 * WRS16_LDS <= 160 * 1024 && WRS16_PITCH >= WRW_SW + 2, "two workgroups per CU; a plane holds an x row segment");
+
+// the staging stores of the WRS_MF_16 image: a thread's float4 (pixel tid / 16 + 16 u, channels 4 (tid % 16) ..+3) -> three 8-byte pieces
+__device__ __forceinline__ void wrs16_store_x(char* xs, int slot, const WrwStage& st, bool rok, const f32x4 (&v)[3]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const int tid = threadIdx.x;
+    char* d = xs + slot * WRS16_SLOT + wrs16_off(0, (tid >> 2) & 3, tid >> 4, 4 * (tid & 3));
+    wrs_store(d, WRS16_PIECE, (rok && st.xok[0]) ? v[0] : zero);
+    wrs_store(d + 16 * WRS16_PIX, WRS16_PIECE, (rok && st.xok[1]) ? v[1] : zero);
+    if (tid + 512 < WRW_XF4) wrs_store(d + 32 * WRS16_PIX, WRS16_PIECE, (rok && st.xok[2]) ? v[2] : zero);
+}
+__device__ __forceinline__ void wrs16_store_dy(char* ds, int buf, const WrwStage& st, const f32x4 (&v)[2]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const int tid = threadIdx.x;
+    char* d = ds + buf * WRS16_SLOT + wrs16_off(0, (tid >> 2) & 3, tid >> 4, 4 * (tid & 3));
+    wrs_store(d, WRS16_PIECE, st.dok[0] ? v[0] : zero);
+    wrs_store(d + 16 * WRS16_PIX, WRS16_PIECE, st.dok[1] ? v[1] : zero);
+}
+// One operand fragment of v_mfma_f32_16x16x32_bf16: the eight pixels wrs16_kpix(g, 0 .. 7) of channel i of a quarter plane.  `blk` =
+// the plane's bytes at the strip row's first pixel (+ kw for x); g = lane / 16, i = lane % 16.  On the device two transposing reads,
+// as wrs_frag; elsewhere the same eight values one by one.
+__device__ __forceinline__ bf16x8 wrs16_frag(const char* blk, int g, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) bf16x4* lds_b64;
+    const char* a = blk + wrs16_off(0, 0, wrs16_kpix(g, 0) + (i >> 2), 4 * (i & 3));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)a);
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)(a + (wrs16_kpix(0, 4) - wrs16_kpix(0, 0)) * WRS16_PIX));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#else
+    bf16x8 f;
+    for (int e = 0; e < 8; ++e) {
+        __bf16 v;
+        __builtin_memcpy(&v, blk + wrs16_off(0, 0, wrs16_kpix(g, e), i), 2);
+        f[e] = v;
+    }
+    return f;
+#endif
+}
+// wrs_flush for the accumulators of WRS_MF_16, [tap][block of 16 output channels][block of 16 input channels].  C layout of the
+// 16 x 16 MFMA: column = lane % 16 (input channel), rows 4 (lane / 16) + e (output channel); pb = the lane's element of the first blocks
+__device__ __forceinline__ void wrs16_flush(float* __restrict__ pb, f32x4 (&acc)[9][2][2], bool add, int cin) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        int o = t * cin;
+        HK_PIN_LOADED(o);                                // (as in wrs_flush)
+        float* q = pb + o;
+        f32x4 v[2][2];
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                v[ob][cb] = acc[t][ob][cb];
+                if (add) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[ob][cb][e] += q[(16 * ob + e) * (9 * cin) + 16 * cb];
+                }
+            }
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    q[(16 * ob + e) * (9 * cin) + 16 * cb] = v[ob][cb][e];
+                    acc[t][ob][cb][e] = 0.f;
+                }
+        __builtin_amdgcn_sched_barrier(0);               // one tap at a time: sixteen loads in flight, not 144
+    }
+}
+
 // As conv3x3_wrw_kernel (same grid, jobs, ring, borders, result), with dynamic LDS of WRS_LDS bytes.  WIDE: x [N][H][W][Cin] with
 // Cin a multiple of 64; a workgroup owns the 64 x 9 x 64 block (Cout slice blockIdx.y, Cin slice blockIdx.z) of dW and reads its 64
 // input channels out of the Cin-wide pixels, part [gridDim.x][Cout][9][Cin].  Not WIDE: Cin = 64, as it was.
-template <bool WIDE>
+// MF = WRS_MF_16 (dynamic LDS WRS16_LDS): the wave's 32 x 32 x 9 tile as 2 x 2 blocks of 16 x 16 per tap (36 f32x4, the same 144
+// registers); one MFMA sums over the strip row's 32 pixels, a (row, tap) is 4 blocks x 6 products = 24 MFMAs of 16 cycles.  The six
+// dy fragments (2 blocks x 3 pieces) are read once per row step and serve all nine taps; the x fragments of a 16-channel block
+// (3 pieces) serve 12 MFMAs, and those of the next (tap, block) are read in front of them.  Same jobs, ring, borders, flush and
+// order of the six products; the two output blocks' chains alternate, so no MFMA waits for the one before it.
+template <bool WIDE, int MF>
 __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                 float* __restrict__ part, int H, int W, int Cout, int nstrips,
                                                                 int nrb, int rpb, int njobs, int Cin) {
+    constexpr bool M32 = MF == WRS_MF_32;
     HK_DYN_LDS16(ldsf);
     char* xs = reinterpret_cast<char*>(ldsf);            // ring of four x row segments: [slot][piece][channel half][34 pixels][32]
-    char* ds = xs + 4 * WRS_XSLOT;                       // two dy row segments: [buf][piece][channel half][32 pixels][32]
+    char* ds = xs + 4 * (M32 ? WRS_XSLOT : WRS16_SLOT);  // two dy row segments: [buf][piece][channel half][32 pixels][32]  (WRS_MF_16: wrs16_off)
     const int tid = threadIdx.x, lane = tid & 63, hf = lane >> 5, l15 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int oh = wave >> 1, ch = wave & 1;            // this wave's 32 output channels x 32 input channels, all nine taps
@@ -332,19 +493,32 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
     const int slice = blockIdx.y, cslice = WIDE ? blockIdx.z : 0;
     const int jb = (int)((long long)blockIdx.x * njobs / gridDim.x), je = (int)((long long)(blockIdx.x + 1) * njobs / gridDim.x);
 
-    f32x16 acc[9];
+    f32x16 acc[9];                                       // WRS_MF_32: [tap]
+    f32x4 acc4[9][2][2];                                 // WRS_MF_16: [tap][block of 16 output channels][block of 16 input channels]
+    if constexpr (M32) {
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+        for (int t = 0; t < 9; ++t)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    } else {
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc4[t][q >> 1][q & 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
 
     const int blk = 8 * hf * WRS_PIX + ((lane >> 4) & 1) * 32;      // this lane's group block inside a plane, first pixel 0
-    const int aoff = oh * WRS_DPLANE + blk, boff = ch * WRS_XPLANE + blk;
-    // this wave's part of the workgroup's partial result (C layout of the 32 x 32 MFMA, as in conv3x3_wrw_kernel).  Every
-    // WRS_FLUSH row steps the accumulators are added to it with ordinary fp32 additions and start again from zero (header: "chains")
+    // (WRS_MF_16: the wave's first dy and x quarter planes; the lane's part of the address is wrs16_frag's)
+    const int aoff = M32 ? oh * WRS_DPLANE + blk : wrs16_off(0, 2 * oh, 0, 0), boff = M32 ? ch * WRS_XPLANE + blk : wrs16_off(0, 2 * ch, 0, 0);
+    // this wave's part of the workgroup's partial result (C layout of the 32 x 32 MFMA, as in conv3x3_wrw_kernel; WRS_MF_16: at
+    // wrs16_flush).  Every WRS_FLUSH row steps the accumulators are added to it with ordinary fp32 additions and start again from
+    // zero (header: "chains")
     auto mine = [&]() {                                  // (made anew at every flush: not two more registers through the row loop)
         const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-        return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 5)) * (9 * cin) + cslice * WRW_CI + (w & 1) * 32 + (l & 31);
+        if constexpr (M32)
+            return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 5)) * (9 * cin) + cslice * WRW_CI + (w & 1) * 32 + (l & 31);
+        else
+            return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 4)) * (9 * cin) + cslice * WRW_CI + (w & 1) * 32 + (l & 15);
     };
     int since = 0;
     bool stored = false;
@@ -376,63 +550,109 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
         for (int t = 0; t < 3; ++t) {
             const bool rok = wrw_load_x(xi, st, r0 - 1 + t, H, W, cin, vx);
             wrw_loads_landed(vx, vd);
-            wrs_store_x(xs, t, st, rok, vx);
+            if constexpr (M32) wrs_store_x(xs, t, st, rok, vx);
+            else wrs16_store_x(xs, t, st, rok, vx);
         }
-        wrs_store_dy(ds, 0, st, vd);
+        if constexpr (M32) wrs_store_dy(ds, 0, st, vd);
+        else wrs16_store_dy(ds, 0, st, vd);
         __syncthreads();
         for (int k = 0; k < nrows; ++k) {
             const bool rok = wrw_load_x(xi, st, r0 + k + 2, H, W, cin, vx);
             wrw_load_dy(dyi, st, r0 + k + 1, H, W, Cout, vd);
-            const char* A = ds + (k & 1) * WRS_DBUF + aoff;
-            const char* B[3] = {xs + (k & 3) * WRS_XSLOT + boff, xs + ((k + 1) & 3) * WRS_XSLOT + boff, xs + ((k + 2) & 3) * WRS_XSLOT + boff};
-            // 18 rounds of six MFMAs: (16-pixel chunk of the row, tap); the fragments of round i + 1 are read before the MFMAs of round i
-            bf16x8 a[3], b[3];
+            constexpr int DBUF = M32 ? WRS_DBUF : WRS16_SLOT, XSLOT = M32 ? WRS_XSLOT : WRS16_SLOT;
+            const char* A = ds + (k & 1) * DBUF + aoff;
+            const char* B[3] = {xs + (k & 3) * XSLOT + boff, xs + ((k + 1) & 3) * XSLOT + boff, xs + ((k + 2) & 3) * XSLOT + boff};
+            if constexpr (!M32) {
+                // 18 rounds of twelve MFMAs: (tap, block of 16 input channels); the x fragments of round i + 1 are read before the
+                // MFMAs of round i.  The first reads in the order of their use: dy mid, x mid, dy hi, x lo, dy lo, x hi
+                const int g = lane >> 4;
+                constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
+                bf16x8 a[2][3], b[3];
 #pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                a[s] = wrs_frag(A + 2 * s * WRS_DPLANE, l15);
-                b[s] = wrs_frag(B[0] + 2 * s * WRS_XPLANE, l15);
-            }
+                for (int pr = 0; pr < 3; ++pr) {
 #pragma unroll
-            for (int i = 0; i < 18; ++i) {
-                const int t = i % 9, cn = (i + 1) / 9, tn = (i + 1) % 9;
-                bf16x8 an[3], bn[3];
-                if (i + 1 < 18) {
+                    for (int ob = 0; ob < 2; ++ob) a[ob][PA[pr]] = wrs16_frag(A + wrs16_off(PA[pr], ob, 0, 0), g, l15);
+                    b[PB[pr]] = wrs16_frag(B[0] + wrs16_off(PB[pr], 0, 0, 0), g, l15);
+                }
 #pragma unroll
-                    for (int s = 0; s < 3; ++s) {
-                        bn[s] = wrs_frag(B[tn / 3] + 2 * s * WRS_XPLANE + (16 * cn + tn % 3) * WRS_PIX, l15);
-                        if (tn == 0) an[s] = wrs_frag(A + 2 * s * WRS_DPLANE + 16 * cn * WRS_PIX, l15);
+                for (int i = 0; i < 18; ++i) {
+                    const int t = i / 2, cb = i % 2, tn = (i + 1) / 2, cbn = (i + 1) % 2;
+                    bf16x8 bn[3];
+                    if (i + 1 < 18) {
+#pragma unroll
+                        for (int s = 0; s < 3; ++s) bn[s] = wrs16_frag(B[tn / 3] + wrs16_off(s, cbn, tn % 3, 0), g, l15);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);   // (as below)
+                    // the same six products in the same order, each into both output blocks before the next
+#pragma unroll
+                    for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+                        for (int ob = 0; ob < 2; ++ob) acc4[t][ob][cb] = mfma_f32_16x16x32_bf16(a[ob][PA[pr]], b[PB[pr]], acc4[t][ob][cb]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (i + 1 < 18) {
+#pragma unroll
+                        for (int s = 0; s < 3; ++s) b[s] = bn[s];
                     }
                 }
-                __builtin_amdgcn_sched_barrier(0);       // (left alone, the scheduler sinks each read to the MFMA that needs it)
-                // the six products of first and second order, small ones first (they meet a running sum either way: the order
-                // costs nothing and matters only in a chain's first steps)
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[t], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (i + 1 < 18) {
+            } else {
+                // 18 rounds of six MFMAs: (16-pixel chunk of the row, tap); the fragments of round i + 1 are read before the MFMAs of round i
+                bf16x8 a[3], b[3];
 #pragma unroll
-                    for (int s = 0; s < 3; ++s) {
-                        b[s] = bn[s];
-                        if (tn == 0) a[s] = an[s];
+                for (int s = 0; s < 3; ++s) {
+                    a[s] = wrs_frag(A + 2 * s * WRS_DPLANE, l15);
+                    b[s] = wrs_frag(B[0] + 2 * s * WRS_XPLANE, l15);
+                }
+#pragma unroll
+                for (int i = 0; i < 18; ++i) {
+                    const int t = i % 9, cn = (i + 1) / 9, tn = (i + 1) % 9;
+                    bf16x8 an[3], bn[3];
+                    if (i + 1 < 18) {
+#pragma unroll
+                        for (int s = 0; s < 3; ++s) {
+                            bn[s] = wrs_frag(B[tn / 3] + 2 * s * WRS_XPLANE + (16 * cn + tn % 3) * WRS_PIX, l15);
+                            if (tn == 0) an[s] = wrs_frag(A + 2 * s * WRS_DPLANE + 16 * cn * WRS_PIX, l15);
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);       // (left alone, the scheduler sinks each read to the MFMA that needs it)
+                    // the six products of first and second order, small ones first (they meet a running sum either way: the order
+                    // costs nothing and matters only in a chain's first steps)
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[t], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (i + 1 < 18) {
+#pragma unroll
+                        for (int s = 0; s < 3; ++s) {
+                            b[s] = bn[s];
+                            if (tn == 0) a[s] = an[s];
+                        }
                     }
                 }
             }
             wrw_loads_landed(vx, vd);
-            wrs_store_x(xs, (k + 3) & 3, st, rok, vx);
-            wrs_store_dy(ds, (k + 1) & 1, st, vd);
+            if constexpr (M32) {
+                wrs_store_x(xs, (k + 3) & 3, st, rok, vx);
+                wrs_store_dy(ds, (k + 1) & 1, st, vd);
+            } else {
+                wrs16_store_x(xs, (k + 3) & 3, st, rok, vx);
+                wrs16_store_dy(ds, (k + 1) & 1, st, vd);
+            }
             __syncthreads();
             if (++since == WRS_FLUSH) {                  // (no load of the next step is in flight yet; each wave owns its part)
-                wrs_flush(mine(), acc, stored, cin);
+                if constexpr (M32) wrs_flush(mine(), acc, stored, cin);
+                else wrs16_flush(mine(), acc4, stored, cin);
                 since = 0;
                 stored = true;
             }
         }
     }
-    if (since > 0 || !stored) wrs_flush(mine(), acc, stored, cin);
+    if (since > 0 || !stored) {
+        if constexpr (M32) wrs_flush(mine(), acc, stored, cin);
+        else wrs16_flush(mine(), acc4, stored, cin);
+    }
 }
 
 // Which calls the split form serves by default (knob wrw_split at -1): the layers where it beat the fp32 form by more than three
@@ -442,6 +662,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_split_kernel(const float* 
 static bool wrw_split_wins(int N, int H, int W, int Cout) {
     const long long pixels = (long long)N * H * W;
     return Cout >= 2 * WRW_OT ? pixels >= 16ll * 224 * 224 : pixels >= 32ll * 448 * 448;
+}
+
+// Which calls of the split form run on the 16 x 16 x 32 MFMA by default (knob wrw_mfma at -1).  A rule in N, H, W and Cout only: a
+// wide call and the 64-channel call over the same map get the same shape (the tests compare them bit for bit).  Decided by the layers'
+// times inside the training step (profiles/wrw_mfma_step_layers.json: HK_WRW_MFMA=1 against =0 on this build and against the build
+// before): all twelve layers faster at batch 64 (0.02 - 0.38 ms each), none slower at batch 16 beyond the traces' spread - always.
+// WRS_MF_32 stays reachable through the knob (tests: held to the bits of the commit before).
+static bool wrw_mfma16_wins(int N, int H, int W, int Cout) {
+    (void)N; (void)H; (void)W; (void)Cout;
+    return true;
 }
 
 // The split of a problem into jobs and workgroups: the row-block height whose heaviest workgroup has the fewest row steps
@@ -475,6 +705,18 @@ static bool wrw_plan(int N, int H, int W, int slices, bool wide, WrwPlan& pl) {
     return best >= 0;
 }
 
+// one instantiation of the split form with its own LDS size (cin = Cin of a wide call, 64 otherwise)
+template <bool WIDE, int MF>
+static int wrw_split_launch(dim3 grid, const float* dy, const float* x, float* part, int H, int W, int Cout, const WrwPlan& pl, int cin,
+                            hk_stream_t stream) {
+    constexpr int LDS = MF == WRS_MF_32 ? WRS_LDS : WRS16_LDS;
+    HK_ALLOW_BIG_LDS((conv3x3_wrw_split_kernel<WIDE, MF>), LDS);
+    hipLaunchKernelGGL((conv3x3_wrw_split_kernel<WIDE, MF>), grid, dim3(256), LDS, (hipStream_t)stream, dy, x, part, H, W, Cout, pl.nstrips,
+                       pl.nrb, pl.rpb, pl.njobs, cin);
+    HK_LAUNCH_CHECK();
+    return HK_OK;
+}
+
 }  // namespace hk
 
 using namespace hk;
@@ -501,14 +743,18 @@ extern "C" int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N,
     WrwPlan pl;
     if (!wrw_plan(N, H, W, oslices * cslices, wide, pl)) return HK_ERR_UNSUPPORTED;
     float* part = (float*)ws;
+    const int mfma = tuning().wrw_mfma;
+    const bool mf16 = mfma == 1 || (mfma < 0 && wrw_mfma16_wins(N, H, W, Cout));
     if (wide) {
-        HK_ALLOW_BIG_LDS(conv3x3_wrw_split_kernel<true>, WRS_LDS);
-        hipLaunchKernelGGL(conv3x3_wrw_split_kernel<true>, dim3((unsigned)pl.nwg, (unsigned)oslices, (unsigned)cslices), dim3(256), WRS_LDS,
-                           (hipStream_t)stream, dy, x, part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs, Cin);
+        const dim3 grid((unsigned)pl.nwg, (unsigned)oslices, (unsigned)cslices);
+        const int e = mf16 ? wrw_split_launch<true, WRS_MF_16>(grid, dy, x, part, H, W, Cout, pl, Cin, stream)
+                           : wrw_split_launch<true, WRS_MF_32>(grid, dy, x, part, H, W, Cout, pl, Cin, stream);
+        if (e != HK_OK) return e;
     } else if (split > 0 || (split < 0 && wrw_split_wins(N, H, W, Cout))) {
-        HK_ALLOW_BIG_LDS(conv3x3_wrw_split_kernel<false>, WRS_LDS);
-        hipLaunchKernelGGL(conv3x3_wrw_split_kernel<false>, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), WRS_LDS,
-                           (hipStream_t)stream, dy, x, part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs, WRW_CI);
+        const dim3 grid((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT));
+        const int e = mf16 ? wrw_split_launch<false, WRS_MF_16>(grid, dy, x, part, H, W, Cout, pl, WRW_CI, stream)
+                           : wrw_split_launch<false, WRS_MF_32>(grid, dy, x, part, H, W, Cout, pl, WRW_CI, stream);
+        if (e != HK_OK) return e;
     } else {
         hipLaunchKernelGGL(conv3x3_wrw_kernel, dim3((unsigned)pl.nwg, (unsigned)(Cout / WRW_OT)), dim3(256), 0, (hipStream_t)stream, dy, x,
                            part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);

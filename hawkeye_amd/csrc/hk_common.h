@@ -63,7 +63,9 @@ struct Tuning {
     int wrw_split = -1;     // HK_WRW_SPLIT     hk_conv3x3_wrw: 0: the fp32-MFMA kernel, 1: the three-way split bf16-MFMA kernel wherever the entry point
                             //                  serves the call, -1: per layer, the measured winner (conv_wrw.hip: wrw_split_wins)
     int wrw_wide = 1;       // HK_WRW_WIDE      hk_conv3x3_wrw with more than 64 input channels (split form only): 1: served, 0: refused (HK_ERR_UNSUPPORTED)
-    int conv_fwd = -1;      // HK_CONV_FWD      forward of the trunk's 3 x 3 convolutions with multiples of 64 channels: -1: hk_conv3x3_fwd for the layers of the
+    int wrw_mfma = -1;      // HK_WRW_MFMA      bf16 MFMA of hk_conv3x3_wrw's split form (conv_wrw.hip, MF): 1: v_mfma_f32_16x16x32_bf16, 0: v_mfma_f32_32x32x16_bf16,
+                            //                  -1: per call, the measured winner (conv_wrw.hip: wrw_mfma16_wins)
+    int conv_fwd = -1;      // HK_CONV_FWD     forward of the trunk's 3 x 3 convolutions with multiples of 64 channels: -1: hk_conv3x3_fwd for the layers of the
                             //                  measured table (functional.CONV_FWD_WINS), 0: the library's everywhere (the entry point refuses), 1: hk_conv3x3_fwd
                             //                  wherever it serves the call (tests)
     int conv_bwd_data = -1; // HK_CONV_BWD_DATA the same for their input gradient: hk_conv3x3_bwd_data, functional.CONV_BWD_DATA_WINS

@@ -71,6 +71,8 @@ const char* hk_version(void);
  *                   the entry point serves the call, -1 (default) = per layer, the measured winner
  *   "wrw_wide"      hk_conv3x3_wrw with more than 64 input channels: 1 (default) = served (by the split form); 0 = refused with
  *                   HK_ERR_UNSUPPORTED, as before the split form read wider pixels
+ *   "wrw_mfma"      the bf16 MFMA the split form of hk_conv3x3_wrw runs on: 1 = v_mfma_f32_16x16x32_bf16, 0 = v_mfma_f32_32x32x16_bf16,
+ *                   -1 (default) = per call, the measured winner (a rule in N, H, W and Cout).  Same bound either way; the bits differ
  *   "conv_fwd"      forward of the trunk's 3 x 3 convolutions with multiples of 64 channels (hawkeye_conv.h): -1 (default) = the split
  *                   bf16-MFMA kernel for the layers of the measured table, 0 = the library's everywhere (the entry point then refuses
  *                   with HK_ERR_UNSUPPORTED), 1 = the kernel wherever the entry point serves the call (tests)

@@ -14,7 +14,13 @@ slices of x) against the library's weight gradient (torch.ops.aten.convolution_b
 and the same bar: a layer is routed if the kernel's slowest repeat is faster than the library's fastest by more than three times
 the library's own min-max spread.  The file is rewritten after every row.
 
-    python tools/wrw_rows.py --set wide [--out profiles/wrw_wide_timing.json]"""
+    python tools/wrw_rows.py --set wide [--out profiles/wrw_wide_timing.json]
+
+--set mfma: all twelve layers at batch 64 and 16, the split form on v_mfma_f32_32x32x16_bf16 (knob wrw_mfma 0) against the same kernel
+on v_mfma_f32_16x16x32_bf16 (1), same calls.  For the record only: the rule behind the knob's default (conv_wrw.hip:
+wrw_mfma16_wins) was decided by the layers' times inside the training step (profiles/wrw_mfma_step_layers.json).
+
+    python tools/wrw_rows.py --set mfma [--out profiles/wrw_mfma_timing.json]"""
 import argparse
 import json
 import os
@@ -123,10 +129,39 @@ def wide_rows(HF, dev, result, out):
             torch.cuda.empty_cache()
 
 
+def mfma_rows(HF, _lib, dev, result, out):
+    """All twelve layers: the split form on either bf16 MFMA."""
+    result['unit'] = ('milliseconds per call of hk_conv3x3_wrw (HIP events around the entry point), knob wrw_split 1: `mfma32` = wrw_mfma 0, '
+                      '`mfma16` = wrw_mfma 1')
+    gen = torch.Generator(device=dev).manual_seed(37)
+    layers = {**{k: (s, 64, c) for k, (s, c) in LAYERS.items()}, **WIDE_LAYERS}
+    for batch in (64, 16):
+        for name, (side, cin, cout) in layers.items():
+            x = torch.empty(batch, cin, side, side, device=dev, memory_format=torch.channels_last).normal_(0.0, 1.0, generator=gen)
+            dy = torch.empty(batch, cout, side, side, device=dev, memory_format=torch.channels_last).normal_(0.0, 1.0, generator=gen)
+            flop = 2.0 * batch * side * side * cout * 9 * cin
+            rows, dw = {}, {}
+            for key, v in (('mfma32', 0), ('mfma16', 1)):
+                with _lib.tuning(wrw_split=1, wrw_mfma=v):
+                    HF.conv3x3_wrw_raw(x[:1], dy[:1])          # (the workspace is allocated outside the timed calls)
+                    rows[key] = row(timed(HF, x, dy), flop)
+                    dw[key] = HF.conv3x3_wrw_raw(x, dy).double()
+            rows['rel_difference_mfma16_vs_mfma32'] = float((dw['mfma16'] - dw['mfma32']).norm() / dw['mfma32'].norm())
+            key = f'{name}_b{batch}'
+            result['rows'][key] = rows
+            m32, m16 = rows['mfma32'], rows['mfma16']
+            result['routing'][key] = {'mfma32_min': m32['min'], 'mfma32_spread': round(m32['max'] - m32['min'], 4), 'mfma16_max': m16['max'],
+                                      'gain_ms': round(m32['min'] - m16['max'], 4), 'min_ratio': round(m16['min'] / m32['min'], 4)}
+            print(key, result['routing'][key], flush=True)
+            write(result, out)
+            del x, dy, dw
+            torch.cuda.empty_cache()
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
-    ap.add_argument('--set', default='split', choices=['split', 'wide'])
+    ap.add_argument('--set', default='split', choices=['split', 'wide', 'mfma'])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print('wrw_rows needs an MI355X: nothing is measured without one')
@@ -138,6 +173,8 @@ if __name__ == '__main__':
     result = {'device': torch.cuda.get_device_name(0), 'warmup_calls': WARMUP, 'timed_calls': CALLS, 'rows': {}, 'routing': {}}
     if args.set == 'wide':
         wide_rows(HF, dev, result, args.out)
+    elif args.set == 'mfma':
+        mfma_rows(HF, _lib, dev, result, args.out)
     else:
         split_rows(HF, _lib, dev, result)
     print(json.dumps(result, indent=1))
