@@ -143,11 +143,22 @@ TRUNK_EPI_SIGNATURES = {
     'hk_conv3x3_masked_bwd_data': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
 }
 
+# the InterpParts plugin's grouping unit and criterion; mirrors include/hawkeye_interp.h one to one
+INTERP_SIGNATURES = {
+    'hk_ip_group_fwd_ws_bytes': (c_sz, [c_i] * 5),
+    'hk_ip_group_fwd': (c_i, [c_f] * 7 + [c_i] * 5 + [c_f, c_sz, c_f]),
+    'hk_ip_group_bwd_ws_bytes': (c_sz, [c_i] * 5),
+    'hk_ip_group_bwd': (c_i, [c_f] * 11 + [c_i] * 5 + [c_f, c_sz, c_f]),
+    'hk_ip_loss_ws_bytes': (c_sz, [c_i, c_i]),
+    'hk_ip_loss': (c_i, [c_f] * 5 + [c_fl] + [c_f] * 3 + [c_i] * 6 + [c_f, c_sz, c_f]),
+}
+
 
 def attach(lib):
-    """Give every function of SIGNATURES, TRUNK_SIGNATURES and TRUNK_EPI_SIGNATURES its prototype on a library object (the gfx950
-    build, or whatever stands in for it).  Returns the library."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()) + list(TRUNK_EPI_SIGNATURES.items()):
+    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES and INTERP_SIGNATURES its prototype on a library
+    object (the gfx950 build, or whatever stands in for it).  Returns the library."""
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()) + list(TRUNK_EPI_SIGNATURES.items()) + \
+            list(INTERP_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args

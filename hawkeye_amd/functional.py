@@ -1488,6 +1488,185 @@ def dcl_swap_law(u8_unswap, u8_swap, grid=(7, 7)):
     return law, index
 
 
+# --------------------------------------------------------------------- InterpParts: region grouping and shaping loss
+IP_MAX_PARTS, IP_MAX_CHANNELS = 32, 1024
+
+
+def _ip_group_args(x, weight, smooth_factor, what):
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise _lib.HawkeyeHipError(f'{what}: x must be [N, C, H, W], got {tuple(x.shape)}')
+    c = x.shape[1]
+    if weight.dim() not in (2, 4) or weight.shape[1] != c or weight.numel() != weight.shape[0] * c:
+        raise _lib.HawkeyeHipError(f'{what}: weight must be [K, {c}, 1, 1] or [K, {c}], got {tuple(weight.shape)}')
+    k = weight.shape[0]
+    if smooth_factor.numel() != k:
+        raise _lib.HawkeyeHipError(f'{what}: smooth_factor must hold {k} values, got {tuple(smooth_factor.shape)}')
+    if not 1 <= k <= IP_MAX_PARTS:
+        raise _lib.HawkeyeHipError(f'{what}: 1 to {IP_MAX_PARTS} parts are served, got {k}')
+    if c % 64 or c > IP_MAX_CHANNELS:
+        raise _lib.HawkeyeHipError(f'{what}: the channel count must be a multiple of 64 up to {IP_MAX_CHANNELS} (the tile is held in LDS), got {c}')
+    _one_device(what, x.device, weight, smooth_factor)
+    return _f32c(x), _f32c(weight).reshape(k, c), _f32c(smooth_factor).reshape(k)
+
+
+def ip_group_bwd(x, weight, smooth_factor, outputs_t, s, nrm, d_outputs_t, d_assign, need=(True, True, True)):
+    """The raw backward of `ip_group` (hk_ip_group_bwd): x [N,C,H,W], weight [K,C], smooth_factor [K], the forward's outputs_t
+    [N,C,K], s and nrm [N,K]; d_outputs_t [N,C,K] and d_assign [N,K,H,W] may each be None, meaning zeros ->
+    (dx, d_weight [K,C], d_smooth_factor [K]), None where `need` says so.  No autograd."""
+    lib = _lib.load()
+    x, weight, smooth_factor = _ip_group_args(x, weight, smooth_factor, 'ip_group_bwd')
+    n, c, h, w = x.shape
+    k = weight.shape[0]
+    outputs_t, s, nrm = (_f32_shaped(t, shape, 'ip_group_bwd', name) for t, shape, name in
+                         ((outputs_t, (n, c, k), 'outputs_t'), (s, (n, k), 's'), (nrm, (n, k), 'nrm')))
+    d_outputs_t = None if d_outputs_t is None else _f32_shaped(d_outputs_t, (n, c, k), 'ip_group_bwd', 'd_outputs_t')
+    d_assign = None if d_assign is None else _f32_shaped(d_assign, (n, k, h, w), 'ip_group_bwd', 'd_assign')
+    dx = torch.empty_like(x) if need[0] else None
+    dwt = torch.empty(k, c, dtype=torch.float32, device=x.device) if need[1] else None
+    dsm = torch.empty(k, dtype=torch.float32, device=x.device) if need[2] else None
+    nws = lib.hk_ip_group_bwd_ws_bytes(n, c, k, h, w)
+    ws = _ws(nws, x.device)
+    check(lib.hk_ip_group_bwd(ptr(x), ptr(weight), ptr(smooth_factor), ptr(outputs_t), ptr(s), ptr(nrm), ptr(d_outputs_t), ptr(d_assign),
+                              ptr(dx), ptr(dwt), ptr(dsm), n, c, k, h, w, ptr(ws), nws, stream()), 'hk_ip_group_bwd')
+    return dx, dwt, dsm
+
+
+class _IPGroup(torch.autograd.Function):
+    """replaces GroupingUnit.forward, model/methods/Interp_Parts.py:56-122."""
+
+    @staticmethod
+    def forward(ctx, x, weight, smooth_factor):
+        lib = _lib.load()
+        ctx.wshape, ctx.sshape = weight.shape, smooth_factor.shape
+        x, weight, smooth_factor = _ip_group_args(x, weight, smooth_factor, 'ip_group')
+        n, c, h, w = x.shape
+        k = weight.shape[0]
+        outputs_t = torch.empty(n, c, k, dtype=torch.float32, device=x.device)
+        assign = torch.empty(n, k, h, w, dtype=torch.float32, device=x.device)
+        s, nrm = (torch.empty(n, k, dtype=torch.float32, device=x.device) for _ in range(2))
+        nws = lib.hk_ip_group_fwd_ws_bytes(n, c, k, h, w)
+        ws = _ws(nws, x.device)
+        check(lib.hk_ip_group_fwd(ptr(x), ptr(weight), ptr(smooth_factor), ptr(outputs_t), ptr(assign), ptr(s), ptr(nrm), n, c, k, h, w,
+                                  ptr(ws), nws, stream()), 'hk_ip_group_fwd')
+        ctx.save_for_backward(x, weight, smooth_factor, outputs_t, s, nrm)
+        ctx.set_materialize_grads(False)                   # an unused output reaches the kernel as a null gradient
+        return outputs_t, assign
+
+    @staticmethod
+    def backward(ctx, d_outputs_t, d_assign):
+        dx, dwt, dsm = ip_group_bwd(*ctx.saved_tensors, d_outputs_t, d_assign, ctx.needs_input_grad)
+        return dx, None if dwt is None else dwt.view(ctx.wshape), None if dsm is None else dsm.view(ctx.sshape)
+
+
+def ip_group(x, weight, smooth_factor):
+    """InterpParts' grouping unit in one read of the map: x [N,C,H,W], weight [K,C,1,1] or [K,C] (the part centres) and
+    smooth_factor [K] (before the sigmoid) -> (outputs_t [N,C,K], assign [N,K,H,W]) as GroupingUnit.forward returns them:
+    assign = softmax_k(min(0, 2 <c_k, x_p> - |x_p|^2 - |c_k|^2) / beta_k), outputs_t the normalised residual coding of the
+    assignment-weighted features, transposed.  1 <= K <= 32, C a multiple of 64 up to 1024.  One autograd node; its backward
+    reads x once and writes dx once; gradients come back in the parameters' own shapes."""
+    return _IPGroup.apply(x, weight, smooth_factor)
+
+
+_IP_CACHE = {}
+
+
+def ip_gaussian_window(radius, std):
+    """The reference's GaussianKernel(radius, std) as a float32 tensor [(2 radius + 1), (2 radius + 1)], bit-equal to it:
+    np.exp per element in float64, stored to float32, then normalised by the float32 sum.  radius 0: [[1.]]."""
+    radius = int(radius)
+    if radius < 0:
+        raise _lib.HawkeyeHipError(f'ip_gaussian_window: radius must not be negative, got {radius}')
+    size = 2 * radius + 1
+    weight = torch.ones(size, size)
+    for i in range(-radius, radius + 1):
+        for j in range(-radius, radius + 1):
+            weight[i + radius][j + radius] = np.exp(-((i * i) + (j * j)) / (2 * std * std))
+    return weight / weight.sum()
+
+
+def ip_beta_prior(batch_size, alpha, beta, device=None):
+    """The reference's update_prior_dist: the inverse CDF of Beta(alpha, beta) at the grid points (2 i + 1) / (2 N) - formed in
+    float32 as the reference does, the inverse taken in float64, rounded to float32 -> [N] on `device`.  alpha == 1:
+    1 - (1 - p)^(1 / beta); beta == 1: p^(1 / alpha); anything else needs scipy.  It depends on the arguments alone: made once
+    per (N, alpha, beta, device) and kept."""
+    n = int(batch_size)
+    if n < 1 or not alpha > 0 or not beta > 0:
+        raise _lib.HawkeyeHipError(f'ip_beta_prior: a positive batch size, alpha and beta are needed, got {batch_size}, {alpha}, {beta}')
+    key = ('prior', n, float(alpha), float(beta), str(device))
+    if key not in _IP_CACHE:
+        grid = (torch.arange(1., 2 * n, 2.).float() / (2 * n)).numpy().astype(np.float64)
+        if float(alpha) == 1.0:
+            icdf = 1.0 - np.power(1.0 - grid, 1.0 / float(beta))
+        elif float(beta) == 1.0:
+            icdf = np.power(grid, 1.0 / float(alpha))
+        else:
+            try:
+                from scipy import stats
+            except ImportError as e:
+                raise _lib.HawkeyeHipError(f'ip_beta_prior: Beta({alpha}, {beta}) has no closed-form inverse CDF here (alpha == 1 or '
+                                           f'beta == 1 have): scipy is needed and is not installed') from e
+            icdf = stats.beta.ppf(grid, a=alpha, b=beta)
+        _IP_CACHE[key] = torch.tensor(icdf).float().to(device) if device is not None else torch.tensor(icdf).float()
+    return _IP_CACHE[key]
+
+
+def _ip_window_on(radius, std, device):
+    key = ('window', int(radius), float(std), str(device))
+    if key not in _IP_CACHE:
+        _IP_CACHE[key] = ip_gaussian_window(radius, std).reshape(-1).to(device)
+    return _IP_CACHE[key]
+
+
+class _IPLoss(torch.autograd.Function):
+    """replaces InterpPartsLoss.__call__ and ShapingLoss, model/loss/InterpParts_loss.py:24-138: the three terms and both
+    gradients from two launches; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, logits, assign, labels, window, prior, coeff, radius):
+        lib = _lib.load()
+        logits, assign = _f32c(logits), _f32c(assign)
+        n, classes = logits.shape
+        _, k, h, w = assign.shape
+        loss = torch.empty(3, dtype=torch.float32, device=logits.device)
+        grads = [torch.empty_like(t) for t in (logits, assign)]
+        nws = lib.hk_ip_loss_ws_bytes(n, k)
+        ws = _ws(nws, logits.device)
+        check(lib.hk_ip_loss(ptr(logits), ptr(labels), ptr(assign), ptr(window), ptr(prior), coeff, ptr(loss), ptr(grads[0]), ptr(grads[1]),
+                             n, classes, k, h, w, radius, ptr(ws), nws, stream()), 'hk_ip_loss')
+        return _loss_forward(ctx, loss, grads)
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        return _loss_backward(ctx, g, 5)
+
+
+def ip_loss_with_terms(logits, assign, labels, radius=2, std=0.4, alpha=1.0, beta=0.001, coeff=0.5, window=None, prior=None):
+    """InterpParts' criterion on the logits [N,classes], the assignment maps [N,K,H,W] and labels [N] -> (total, the device
+    tensor [cross entropy, shaping], not differentiable).  shaping: each map blurred with the Gaussian window ("valid"), its
+    maximum, the N maxima of a part sorted and compared in log space with the Beta(alpha, beta) prior's inverse CDF; total =
+    cross entropy + coeff shaping.  The gradient reaches `assign` at the window around each argmax only.  Ties: the lowest
+    flat index, the lower sample first.  No host synchronisation: the window and the prior are made once per configuration
+    (`window` [(2 radius + 1)^2] and `prior` [N] on the device override them)."""
+    what = 'ip_loss'
+    if logits.dim() != 2 or assign.dim() != 4 or min(logits.shape) < 1 or min(assign.shape) < 1 or logits.shape[0] != assign.shape[0]:
+        raise _lib.HawkeyeHipError(f'{what}: logits [N, classes] and assign [N, K, H, W] of one N are needed, got {tuple(logits.shape)} and '
+                                   f'{tuple(assign.shape)}')
+    n, dev, radius = logits.shape[0], logits.device, int(radius)
+    _one_device(what, dev, assign)
+    size = 2 * radius + 1
+    if radius < 0 or assign.shape[2] < size or assign.shape[3] < size:                       # the reference's conv2d raises there
+        raise _lib.HawkeyeHipError(f'{what}: a {assign.shape[2]} x {assign.shape[3]} map is smaller than the {size} x {size} window')
+    y = _int_tensor(labels, (n,), torch.int64, dev, what, 'labels')
+    window = _ip_window_on(radius, std, dev) if window is None else _f32_shaped(window.reshape(-1), (size * size,), what, 'window')
+    prior = ip_beta_prior(n, alpha, beta, dev) if prior is None else _f32_shaped(prior, (n,), what, 'prior')
+    _one_device(what, dev, window, prior)
+    return _IPLoss.apply(logits, assign, y, window, prior, float(coeff), radius)
+
+
+def ip_loss(logits, assign, labels, radius=2, std=0.4, alpha=1.0, beta=0.001, coeff=0.5, window=None, prior=None):
+    return ip_loss_with_terms(logits, assign, labels, radius, std, alpha, beta, coeff, window, prior)[0]
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

@@ -5,3 +5,4 @@ from .APINet_loss import APINetLoss  # noqa: F401
 from .NTS_loss import NTSLoss  # noqa: F401
 from .CrossX_loss import CrossXLoss  # noqa: F401
 from .DCL_loss import DCLLoss  # noqa: F401
+from .InterpParts_loss import InterpPartsLoss  # noqa: F401

@@ -674,5 +674,6 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 
 #include "hawkeye_conv.h" /* the trunk's forward and input gradient */
 #include "hawkeye_conv_epi.h" /* ... with the trunk's epilogue passes done inside those kernels */
+#include "hawkeye_interp.h" /* the InterpParts plugin: region grouping and the shaping loss */
 
 #endif /* HAWKEYE_HIP_H */
