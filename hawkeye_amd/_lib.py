@@ -143,6 +143,11 @@ TRUNK_EPI_SIGNATURES = {
     'hk_conv3x3_masked_bwd_data': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
 }
 
+# ... and how those kernels tile a map (knob `conv_tile`); mirrors include/hawkeye_conv_tile.h one to one
+TRUNK_TILE_SIGNATURES = {
+    'hk_conv3x3_tile_plan': (c_i, [c_i, c_i, c_i, c_i, c_f]),     # (5th: int[12] on the HOST)
+}
+
 # the InterpParts plugin's grouping unit and criterion; mirrors include/hawkeye_interp.h one to one
 INTERP_SIGNATURES = {
     'hk_ip_group_fwd_ws_bytes': (c_sz, [c_i] * 5),
@@ -155,10 +160,10 @@ INTERP_SIGNATURES = {
 
 
 def attach(lib):
-    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES and INTERP_SIGNATURES its prototype on a library
-    object (the gfx950 build, or whatever stands in for it).  Returns the library."""
+    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES, TRUNK_TILE_SIGNATURES and INTERP_SIGNATURES its
+    prototype on a library object (the gfx950 build, or whatever stands in for it).  Returns the library."""
     for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()) + list(TRUNK_EPI_SIGNATURES.items()) + \
-            list(INTERP_SIGNATURES.items()):
+            list(TRUNK_TILE_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args

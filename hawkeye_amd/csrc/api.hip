@@ -25,7 +25,7 @@ const Knob kKnobs[] = {
     {"wrw_split", "HK_WRW_SPLIT", &Tuning::wrw_split},          {"wrw_wide", "HK_WRW_WIDE", &Tuning::wrw_wide},
     {"conv_fwd", "HK_CONV_FWD", &Tuning::conv_fwd},             {"conv_bwd_data", "HK_CONV_BWD_DATA", &Tuning::conv_bwd_data},
     {"conv_epi", "HK_CONV_EPI", &Tuning::conv_epi},             {"conv_mfma", "HK_CONV_MFMA", &Tuning::conv_mfma},
-    {"wrw_mfma", "HK_WRW_MFMA", &Tuning::wrw_mfma},
+    {"wrw_mfma", "HK_WRW_MFMA", &Tuning::wrw_mfma},             {"conv_tile", "HK_CONV_TILE", &Tuning::conv_tile},
 };
 Tuning from_env() {
     Tuning t;

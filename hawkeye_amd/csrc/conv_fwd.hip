@@ -14,6 +14,14 @@
 //              MFMA blocks (co 0 - 31, 32 - 63) x 32 pixels.  The weights are the operand whose index is the accumulator ROW, so a
 //              lane ends with 4 consecutive output channels of one pixel per accumulator quad: 16-byte stores, 128 contiguous
 //              bytes per pixel and block.  Nothing is accumulated in memory: no atomics, no split-K, no zero-fill, same bits each run
+//   tiles    = which 128 pixels a workgroup takes is a third template parameter (G, PLAN, documented at CfGeo and at the kernel; knob
+//              `conv_tile`): 4 x 32 as described here, 8 x 16 (two rows a wave; halo tile 10 x 18) or, on CF_MF_16, 16 x 8 (four rows a wave;
+//              halo tile 18 x 10 at a pitch of 16 pixels, 79872 B of LDS).  4 x 32 pads a 112-wide map to 128 columns and a 56-wide one
+//              to 64 - one MFMA in eight on columns the store throws away; conv3x3_plan takes per map the tiling with the fewest tiles:
+//              112 wide 98 tiles an image for 112 (8 x 16), 56 wide 25 for 28 (8 x 16 over three strips + 16 x 8 over the last eight
+//              columns, one launch).  Every output element keeps its products, their order and its bits.  Measured at batch 64 (DESIGN
+//              3.10, "Tile geometries"): matrix-pipe cycles x 0.875 and x 0.893 as the tile counts say, the clock gives 3 % back, the
+//              twelve launches at those widths 0.17 - 0.60 ms faster each, the step 106.3 -> 102.1 ms
 //   K        = the channel axis, contiguous in NHWC x and in [co][tap][ci] weights: a fragment (8 consecutive k of one row) is 16
 //              contiguous bytes of a [pixel][32 channels] bf16 plane - a plain ds_read_b128.  Planes have a pitch of 80 bytes a
 //              pixel (5 l mod 16 is a permutation of the 16-byte slots of a 256-byte bank row: the 16 lanes of a read phase do not meet)
@@ -53,6 +61,7 @@
 //              fewer cycles (LDS bank conflicts 7 % -> 0, a fifth less weight traffic) at a 3 - 4 % higher clock, the matrix pipe
 //              61 - 72 % busy.  Routed per layer, direction and batch by functional.py's measured table.  Registers
 //              with the weight tiles by DMA and every fragment read in front of the MFMAs: 204 - 206 VGPRs (MF = 0: 190 - 192), no spill
+//              (8 x 16: 200 - 202 and 184 - 188; the launch with both 8 x 16 and 16 x 8: 206 - 208)
 #include "hk_common.h"
 #include "hk_split_bf16.h"
 #include <hk_mfma_bf16.h>   // the 16 x 16 x 32 bf16 MFMA (the emulation build finds its model of it first)
@@ -85,6 +94,49 @@ constexpr int CF16_XPLANE = CF_HPIX * CF16_PIX;          // 13056 B
 constexpr int CF16_WPLANE = CF_CO * CF16_PIX;            // 4096 B
 constexpr int CF16_WTAP = 3 * CF16_WPLANE;               // 12288 B: three 16-byte loads a thread
 constexpr int CF16_LDS = 3 * CF16_XPLANE + 2 * CF16_WTAP;  // 63744 B
+
+// G, which 128 pixels a workgroup takes ("Tile geometries"): the constants above are those of 4 rows x 32 columns, whose
+// strips pad a 112-wide map to 128 columns and a 56-wide one to 64 - one MFMA in eight on zeros.  8 x 16 (halo tile 10 x 18, fewer
+// pixels than 6 x 34) tiles 112 = 7 x 16 exactly; 16 x 8 takes the remainder strip of a 56-wide map (3 x 16 + 8).  Everything else is
+// the same: 64 channels x 128 pixels a workgroup, 32 pixels a wave, the same chunks, taps, products and chains for every output
+// element - only the lane that holds it differs
+//   CF_MF_16: wave w, pixel block pb, lane l15 ->  4 x 32: row w, column 16 pb + l15;  8 x 16: row 2 w + pb, column l15;
+//             16 x 8: row 4 w + 2 pb + l15 / 8, column l15 % 8 (halo rows at a pitch of 16 pixels: a tap's row step and the pixel blocks'
+//             distance are then constant offsets in the image, and the lane pattern is conflict-free - it is 2-way conflicted at 10 .. 15)
+//   CF_MF_32: wave w, lane l31 -> 4 x 32: row w, column l31;  8 x 16: row 2 w + l31 / 16, column l31 % 16 for the first row and
+//             (l31 - 2) % 16 for the second: the halo pitch of 18 moves the second row's pixels 2 slots on, the rotation takes
+//             them back, so a ds_read_b128 lane group (which mixes lanes of both halves) meets the slots of 4 x 32.  No 16 x 8
+constexpr int CF_G_4x32 = 0, CF_G_8x16 = 1, CF_G_16x8 = 2;
+template <int G>
+struct CfGeo {
+    static constexpr int TH = G == CF_G_4x32 ? 4 : (G == CF_G_8x16 ? 8 : 16), TW = 128 / TH;      // output rows and columns of a tile
+    static constexpr int HR = TH + 2, HC = TW + 2;           // rows and columns of the halo tile
+    static constexpr int HP = G == CF_G_16x8 ? 16 : HC;      // pixels from one halo row to the next in a plane
+    static constexpr int LPIX = HR * HP;                     // pixels of a plane: 204, 180, 288
+    static constexpr int XF4 = HR * HC * (CF_CK / 4);        // float4 of a halo tile: 1632, 1440, 1440
+    static constexpr int XU = (XF4 + 255) / 256;             // loads per thread: 7, 6, 6
+    static constexpr int PBD = G == CF_G_4x32 ? 16 : (G == CF_G_8x16 ? HP : 2 * HP);      // CF_MF_16: plane pixels from pixel block 0 to 1
+    // a lane's pixel of the tile (CF_MF_16: l = lane % 16 of pixel block pb; CF_MF_32: l = lane % 32, pb = 0)
+    __host__ __device__ static constexpr int trow(bool m32, int wave, int pb, int l) {
+        return G == CF_G_4x32 ? wave : (G == CF_G_8x16 ? 2 * wave + (m32 ? l >> 4 : pb) : 4 * wave + 2 * pb + (l >> 3));
+    }
+    __host__ __device__ static constexpr int tcol(bool m32, int pb, int l) {
+        return G == CF_G_4x32 ? (m32 ? l : 16 * pb + l) : (G == CF_G_8x16 ? (m32 ? (l < 16 ? l : (l - 2) & 15) : l) : l & 7);
+    }
+};
+static_assert(CfGeo<CF_G_4x32>::LPIX == CF_HPIX && CfGeo<CF_G_4x32>::XU == CF_XU && CfGeo<CF_G_4x32>::HP == CF_HW, "4 x 32 is the tile above");
+// PLAN, what a launch tiles a map with: one geometry, or - CF_MF_16 only - 8 x 16 over the whole strips of 16 columns and 16 x 8 over
+// the remainder (a workgroup decodes its region from the tile index); the LDS of a launch is that of its largest geometry
+constexpr int CF_PLAN_4x32 = 0, CF_PLAN_8x16 = 1, CF_PLAN_MIXED = 2;
+template <int MF, int G>
+constexpr int cf_xplane() { return CfGeo<G>::LPIX * (MF == CF_MF_32 ? CF_PIX : CF16_PIX); }
+template <int MF, int PLAN>
+constexpr int cf_lds() {
+    return 3 * cf_xplane<MF, PLAN == CF_PLAN_MIXED ? CF_G_16x8 : PLAN>() + 2 * (MF == CF_MF_32 ? CF_WTAP : CF16_WTAP);
+}
+static_assert(cf_lds<CF_MF_32, CF_PLAN_4x32>() == CF_LDS && cf_lds<CF_MF_16, CF_PLAN_4x32>() == CF16_LDS, "4 x 32 keeps its LDS");
+static_assert(cf_lds<CF_MF_32, CF_PLAN_8x16>() <= CF_LDS && cf_lds<CF_MF_16, CF_PLAN_MIXED>() == 79872 && 2 * 79872 <= 160 * 1024,
+              "two workgroups per CU with every plan");
 // The barrier that ends a tap: s_waitcnt vmcnt(n) lgkmcnt(0) + s_barrier.  HK_VM_BARRIER(n) with the LDS reads waited for as well: the
 // DMA that another wave issues behind this barrier goes into the buffer this tap read, so no fragment read may still be on its way
 // (the reads are issued in front of the MFMAs: the wait finds them done), and no __syncthreads(), whose fence drains vmcnt(0)
@@ -107,19 +159,46 @@ constexpr int CF_B128_GROUPS[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 
                                        {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                        {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
                                        {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+// ... with the lane pattern of geometry G: lane l15 reads pixel base + (its row of the pixel block) HP + (its column); the weights'
+// pattern - 16 consecutive rows - is that of 4 x 32
+template <int G>
 constexpr bool cf16_group_conflict_free(int g) {
-    for (int base = 0; base + 16 <= CF_HPIX; ++base) {    // the fragment's first row: any pixel of the halo tile (weights: multiples of 16)
+    constexpr int LAST = CfGeo<G>::trow(false, 0, 0, 15) * CfGeo<G>::HP + CfGeo<G>::tcol(false, 0, 15);
+    for (int base = 0; base + LAST < CfGeo<G>::LPIX; ++base) {    // the fragment's first pixel: any pixel of the halo tile (weights: multiples of 16)
         unsigned seen = 0;
         for (int i = 0; i < 16; ++i) {
-            const int lane = CF_B128_GROUPS[g][i], slot = (cf16_off(base + (lane & 15), lane >> 4) >> 4) & 15;
+            const int lane = CF_B128_GROUPS[g][i], l = lane & 15;
+            const int pix = base + CfGeo<G>::trow(false, 0, 0, l) * CfGeo<G>::HP + CfGeo<G>::tcol(false, 0, l);
+            const int slot = (cf16_off(pix, lane >> 4) >> 4) & 15;
             if ((seen >> slot) & 1u) return false;
             seen |= 1u << slot;
         }
     }
     return true;
 }
-static_assert(cf16_group_conflict_free(0) && cf16_group_conflict_free(1) && cf16_group_conflict_free(2) && cf16_group_conflict_free(3),
-              "every ds_read_b128 lane group of a CF_MF_16 fragment reads 16 different slots");
+template <int G>
+constexpr bool cf16_conflict_free() {
+    return cf16_group_conflict_free<G>(0) && cf16_group_conflict_free<G>(1) && cf16_group_conflict_free<G>(2) && cf16_group_conflict_free<G>(3);
+}
+static_assert(cf16_conflict_free<CF_G_4x32>() && cf16_conflict_free<CF_G_8x16>() && cf16_conflict_free<CF_G_16x8>(),
+              "every ds_read_b128 lane group of a CF_MF_16 fragment reads 16 different slots, in every geometry at its pitch");
+// the same for the pixel fragment of CF_MF_32 (80-byte pitch: slot 5 pixel + lane / 32 + 2 ks), whose 32 lanes are two tile rows in 8 x 16
+template <int G>
+constexpr bool cf32_conflict_free() {
+    for (int g = 0; g < 4; ++g)
+        for (int base = 0; base + CfGeo<G>::HP + 16 < CfGeo<G>::LPIX; ++base) {
+            unsigned seen = 0;
+            for (int i = 0; i < 16; ++i) {
+                const int lane = CF_B128_GROUPS[g][i], l = lane & 31;
+                const int pix = base + CfGeo<G>::trow(true, 0, 0, l) * CfGeo<G>::HP + CfGeo<G>::tcol(true, 0, l);
+                const int slot = ((pix * CF_PIX + (lane >> 5) * 16) >> 4) & 15;
+                if ((seen >> slot) & 1u) return false;
+                seen |= 1u << slot;
+            }
+        }
+    return true;
+}
+static_assert(cf32_conflict_free<CF_G_4x32>() && cf32_conflict_free<CF_G_8x16>(), "the CF_MF_32 pixel fragment, both geometries");
 static_assert(cf16_off(16, 1) == cf16_off(0, 1) + 16 * CF16_PIX && cf16_off(35, 2) == cf16_off(3, 2) + 32 * CF16_PIX,
               "rows 16 and 32 further on are a constant offset away");
 static_assert(CF16_WTAP <= CF_WTAP && CF16_WTAP == 3 * 256 * 16, "the workspace holds either image; a weight tile is three loads a thread");
@@ -189,19 +268,20 @@ __device__ __forceinline__ unsigned cf_sign4(f32x4 r) {             // the mask 
 }
 
 // The way out of the CF_MF_16 main loop (the kernel's comment: EPI, MF).  C layout of the 16 x 16 MFMA: column = lane & 15 (pixel
-// 16 pb + l15 of the wave's row), row = 4 (lane >> 4) + e (channel 16 cb + 4 kg + e): v[cb][pb] is channel quad 4 cb + kg of pixel pb
-template <int EPI>
+// l15 of the wave's pixel block pb: CfGeo), row = 4 (lane >> 4) + e (channel 16 cb + 4 kg + e): v[cb][pb] is channel quad 4 cb + kg of pixel pb
+template <int EPI, int G>
 __device__ __forceinline__ void cf16_epilogue(const f32x4 (&acc4)[4][2], const f32x4 (&sum4)[4][2], float* ldsf, float* __restrict__ y, int H,
                                               int W, int Cout, long long n, int r0, int c0, int cot, int tile, int wave, int tid, int l15,
                                               int kg, const float* __restrict__ bias, uint8_t* __restrict__ mk,
                                               double* __restrict__ part) {
-    const int row = r0 + wave, c4 = Cout / 4;
+    typedef CfGeo<G> GE;
+    const int c4 = Cout / 4;
     bool live[2];
     long long pix[2];                                                // (used where live)
     f32x4 v[4][2];
 #pragma unroll
     for (int pb = 0; pb < 2; ++pb) {
-        const int col = c0 + 16 * pb + l15;
+        const int row = r0 + GE::trow(false, wave, pb, l15), col = c0 + GE::tcol(false, pb, l15);
         live[pb] = row < H && col < W;
         pix[pb] = (n * H + row) * W + col;
 #pragma unroll
@@ -258,7 +338,7 @@ __device__ __forceinline__ void cf16_epilogue(const f32x4 (&acc4)[4][2], const f
         float* park = ldsf;                                          // every wave is past the last tap's barrier
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
-            float* mine = park + (wave * CF_SW + 16 * pb + l15) * CF_PARK + 4 * kg;
+            float* mine = park + (GE::trow(false, wave, pb, l15) * GE::TW + GE::tcol(false, pb, l15)) * CF_PARK + 4 * kg;
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) *reinterpret_cast<f32x4*>(mine + 16 * cb) = v[cb][pb];
         }
@@ -288,8 +368,8 @@ __device__ __forceinline__ void cf16_epilogue(const f32x4 (&acc4)[4][2], const f
     }
 }
 
-// x [N][H][W][Cin], ws as conv3x3_wsplit_kernel leaves it -> y [N][H][W][Cout].  grid xcd_grid(ntiles, Cout / 64), dynamic LDS CF_LDS.
-// tile = ((n nrb + rb) nstrips + strip): rows [4 rb, 4 rb + 4), columns [32 strip, 32 strip + 32)
+// x [N][H][W][Cin], ws as conv3x3_wsplit_kernel leaves it -> y [N][H][W][Cout]: the work of one workgroup (the kernel, behind this
+// function, decodes the tile; written for 4 x 32, the other geometries: CfGeo)
 //
 // EPI, what happens to the accumulators on their way out (the main loop is the same code in all four):
 //   CF_EPI_NONE  y = the sums                                                                    (hk_conv3x3_fwd, hk_conv3x3_bwd_data)
@@ -297,7 +377,7 @@ __device__ __forceinline__ void cf16_epilogue(const f32x4 (&acc4)[4][2], const f
 //                bias_relu_fwd_kernel<true> (trunk.hip).  A lane holds the even (hf = 0) or the odd quads of its pixel: the two
 //                lanes swap their eight bytes and each stores eight consecutive ones
 //   CF_EPI_POOL  y = p [N][H / 2][W / 2][Cout] = maxpool2x2(relu4(sums + bias)), mk = the 2-bit argmax codes, both exactly as
-//                bias_relu_pool_fwd_kernel forms them (H, W even: a tile anchored at multiples of 4 and 32 holds whole windows).  The
+//                bias_relu_pool_fwd_kernel forms them (H, W even: every geometry is anchored at even rows and columns: a tile holds whole windows).  The
 //                full-resolution map is never written: every wave parks its row in the LDS the last tap has left free, and after one
 //                barrier a thread forms two pooled float4; the 16 lanes of a pooled pixel gather their code bytes into two 8-byte stores
 //   CF_EPI_MASK  y = sums where the bit of mk (read: the sign mask of the map this call produces the gradient of) is set, else 0 -
@@ -314,51 +394,58 @@ __device__ __forceinline__ void cf16_epilogue(const f32x4 (&acc4)[4][2], const f
 // stores four consecutive bytes a pixel), CF_EPI_POOL parks the same [row][column][channel] tile and leaves by the same code, CF_EPI_MASK
 // adds a lane's two pixels and runs the halving butterfly over 16 lanes (all in fp64, a fixed order: db stays the float next to the
 // exact sum)
-template <int EPI, int MF>
-__global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __restrict__ x, const char* __restrict__ ws,
-                                                               float* __restrict__ y, int H, int W, int Cin, int Cout, int nstrips,
-                                                               int nrb, int ntiles, const float* __restrict__ bias,
-                                                               uint8_t* __restrict__ mk, double* __restrict__ part) {
+//
+// G, the tile's geometry (CfGeo): the body below is the kernel for one tile - rows [r0, r0 + TH), columns [c0, c0 + TW) of image n, tile
+// number `tile` of the launch; the kernel itself (conv3x3_split_kernel, behind it) only decodes those from the block index
+template <int EPI, int MF, int G>
+__device__ __forceinline__ void conv3x3_split_tile(float* ldsf, const float* __restrict__ x, const char* __restrict__ ws, float* __restrict__ y,
+                                                   int H, int W, int Cin, int Cout, long long n, int r0, int c0, int tile, int cot,
+                                                   const float* __restrict__ bias, uint8_t* __restrict__ mk, double* __restrict__ part) {
+    typedef CfGeo<G> GE;
     constexpr bool M32 = MF == CF_MF_32;
-    constexpr int XPLANE = M32 ? CF_XPLANE : CF16_XPLANE, WTAP = M32 ? CF_WTAP : CF16_WTAP;
-    HK_DYN_LDS16(ldsf);
-    char* xs = reinterpret_cast<char*>(ldsf);            // the halo tile of the chunk: [piece][6 x 34 pixels][80 B] (CF_MF_16: cf16_off)
+    static_assert(!(M32 && G == CF_G_16x8), "16 x 8 is a geometry of CF_MF_16 only");
+    constexpr int XPLANE = cf_xplane<MF, G>(), WTAP = M32 ? CF_WTAP : CF16_WTAP;
+    constexpr int XU = GE::XU, XF4 = GE::XF4, HC = GE::HC, HP = GE::HP;
+    char* xs = reinterpret_cast<char*>(ldsf);            // the halo tile of the chunk: [piece][HR x HP pixels][80 B] (CF_MF_16: cf16_off)
     char* wb = xs + 3 * XPLANE;                          // two weight tiles: [buf][piece][64 co][80 B] (CF_MF_16: cf16_off)
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
     const int l15 = lane & 15, kg = lane >> 4;           // (CF_MF_16: the lane's row or column of a block, and its k-group)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ncot = Cout / CF_CO, nchunk = Cin / CF_CK, total = nchunk * 9;
-    int tile, cot;
-    if (!xcd_map(blockIdx.x, ntiles, ncot, tile, cot)) return;
-    const int strip = tile % nstrips, tr = tile / nstrips;
-    const int rb = tr % nrb;
-    const long long n = tr / nrb;
-    const int c0 = strip * CF_SW, r0 = rb * CF_R;
+    const int nchunk = Cin / CF_CK, total = nchunk * 9;
     const float* xi = x + n * H * W * Cin;
     const char* wt = ws + (size_t)cot * total * WTAP + tid * 16;
 
-    // this thread's float4 loads of a halo tile: float4 idx -> pixel idx / 8 (row r0 - 1 + pixel / 34, column c0 - 1 + pixel % 34),
+    // this thread's float4 loads of a halo tile: float4 idx -> pixel idx / 8 (row r0 - 1 + pixel / HC, column c0 - 1 + pixel % HC),
     // channels 4 (idx % 8) ..+3 of the chunk; clamped into the image, and whether they count
-    long long xoff[CF_XU];
+    long long xoff[XU];
     unsigned xok = 0;
 #pragma unroll
-    for (int u = 0; u < CF_XU; ++u) {
+    for (int u = 0; u < XU; ++u) {
         const int idx = tid + 256 * u;
-        const bool in = idx < CF_XF4;
-        const int p = in ? idx >> 3 : 0, hr = p / CF_HW, hc = p - hr * CF_HW;
+        const bool in = idx < XF4;
+        const int p = in ? idx >> 3 : 0, hr = p / HC, hc = p - hr * HC;
         const int row = r0 - 1 + hr, col = c0 - 1 + hc;
         if (in && row >= 0 && row < H && col >= 0 && col < W) xok |= 1u << u;
         const int rc = row < 0 ? 0 : (row < H ? row : H - 1), cc = col < 0 ? 0 : (col < W ? col : W - 1);
         xoff[u] = ((long long)rc * W + cc) * Cin + 4 * (idx & 7);
     }
-    // (CF_MF_16: pixel tid / 8 + 32 u, k-group (tid & 7) / 2, its first or second four k)
+    // (CF_MF_16: pixel tid / 8 + 32 u, k-group (tid & 7) / 2, its first or second four k).  Where the plane's pitch is the halo tile's
+    // width the pixel's place is its number; 16 x 8 works it out per load (xdst_of)
     const int xdst = M32 ? (tid >> 3) * CF_PIX + (tid & 7) * 8 : cf16_off(tid >> 3, (tid & 7) >> 1) + (tid & 1) * 8;      // + 32 u pixels
+    auto xdst_of = [&](int u) {
+        if constexpr (HP == HC) {
+            return xdst + u * 32 * (M32 ? CF_PIX : CF16_PIX);
+        } else {
+            const int p = (tid >> 3) + 32 * u, hr = p / HC;
+            return cf16_off(hr * HP + (p - hr * HC), (tid & 7) >> 1) + (tid & 1) * 8;
+        }
+    };
 
-    f32x4 vx[CF_XU];
+    f32x4 vx[XU];
     auto load_x = [&](int chunk) {
         const float* b = xi + chunk * CF_CK;
 #pragma unroll
-        for (int u = 0; u < CF_XU; ++u) HK_LOAD16_ASYNC(vx[u], b + xoff[u]);
+        for (int u = 0; u < XU; ++u) HK_LOAD16_ASYNC(vx[u], b + xoff[u]);
     };
     // tile `it` on its way into buffer `buf` by LDS-DMA, no register in between: the workspace IS the LDS image, and a wave's 64 lanes
     // x 16 bytes are 1 KiB contiguous in both - what one glds16 copies (LDS base wave-uniform, lane l lands at + 16 l).  CF_MF_32: the
@@ -375,12 +462,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     auto store_x = [&]() {
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int u = 0; u < CF_XU; ++u) {
-            if (tid + 256 * u < CF_XF4) {
+        for (int u = 0; u < XU; ++u) {
+            if (tid + 256 * u < XF4) {
                 bf16x4 p[3];
                 wrs_split(((xok >> u) & 1) ? vx[u] : zero, p);
+                const int d = xdst_of(u);
 #pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(xs + s * XPLANE + xdst + u * 32 * (M32 ? CF_PIX : CF16_PIX)) = p[s];
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x4*>(xs + s * XPLANE + d) = p[s];
             }
         }
     };
@@ -405,12 +493,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     load_x(0);
     __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));         // (this wave's pieces of tile 0 have landed, too)
 #pragma unroll
-    for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
+    for (int u = 0; u < XU; ++u) HK_PIN_LOADED(vx[u]);
     store_x();
     HK_LDS_BARRIER();
 
     const int aoff = l31 * CF_PIX + hf * 16;                        // this lane's weight row (+ 32 rows for the second block)
-    const int boff = (wave * CF_HW + l31) * CF_PIX + hf * 16;       // this lane's pixel at tap (0, 0)
+    const int boff = (GE::trow(true, wave, 0, l31) * HP + GE::tcol(true, 0, l31)) * CF_PIX + hf * 16;      // this lane's pixel at tap (0, 0)
+    const int bpix = GE::trow(false, wave, 0, l15) * HP + GE::tcol(false, 0, l15);      // CF_MF_16: the same, as a pixel of the plane, block 0
     int since = 0;
     for (int chunk = 0; chunk < nchunk; ++chunk) {
         const bool more = chunk + 1 < nchunk;
@@ -424,13 +513,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
             if (tap == 5) load_x(more ? chunk + 1 : chunk);
             if constexpr (M32) {
             const char* A = wb + (it & 1) * CF_WTAP + aoff;
-            const char* B = xs + boff + ((tap / 3) * CF_HW + tap % 3) * CF_PIX;
+            const char* B = xs + boff + ((tap / 3) * HP + tap % 3) * CF_PIX;
             bf16x8 a[2][2][3], b[2][3];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int s = 0; s < 3; ++s) {
-                    b[ks][s] = cf_frag(B + s * CF_XPLANE + ks * 32);
+                    b[ks][s] = cf_frag(B + s * XPLANE + ks * 32);
                     a[ks][0][s] = cf_frag(A + s * CF_WPLANE + ks * 32);
                     a[ks][1][s] = cf_frag(A + s * CF_WPLANE + 32 * CF_PIX + ks * 32);
                 }
@@ -448,14 +537,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
                     acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][cb][0], b[ks][0], acc[cb], 0, 0, 0);
                 }
             } else {
-                // the lane's pixel of this tap, first pixel block; its image offset depends on the pixel (cf16_off)
+                // the lane's pixels of this tap, one per pixel block; the image offset depends on the pixel (cf16_off): a constant
+                // from block 0 to block 1 where they are a multiple of 16 pixels apart, worked out for both otherwise (8 x 16: 18 pixels)
                 const char* A = wb + (it & 1) * CF16_WTAP + cf16_off(l15, kg);
-                const char* B = xs + cf16_off(wave * CF_HW + l15 + (tap / 3) * CF_HW + tap % 3, kg);
+                const int bp = bpix + (tap / 3) * HP + tap % 3;
+                const char* Bp[2];
+                Bp[0] = xs + cf16_off(bp, kg);
+                Bp[1] = GE::PBD % 16 == 0 ? Bp[0] + GE::PBD * CF16_PIX : xs + cf16_off(bp + GE::PBD, kg);
                 bf16x8 a[4][3], b[2][3];
 #pragma unroll
                 for (int s = 0; s < 3; ++s) {
 #pragma unroll
-                    for (int pb = 0; pb < 2; ++pb) b[pb][s] = cf_frag(B + s * CF16_XPLANE + pb * 16 * CF16_PIX);
+                    for (int pb = 0; pb < 2; ++pb) b[pb][s] = cf_frag(Bp[pb] + s * XPLANE);
 #pragma unroll
                     for (int cb = 0; cb < 4; ++cb) a[cb][s] = cf_frag(A + s * CF16_WPLANE + cb * 16 * CF16_PIX);
                 }
@@ -470,13 +563,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
                         for (int pb = 0; pb < 2; ++pb) acc4[cb][pb] = mfma_f32_16x16x32_bf16(a[cb][PA[pr]], b[pb][PB[pr]], acc4[cb][pb]);
             }
             // The tap ends with a counted wait and a raw barrier: tile it + 1 has landed for every wave, and every wave has read this
-            // tap's buffer.  Requests retire in order and the weight pieces were issued first: at tap 5 the seven x loads behind them
+            // tap's buffer.  Requests retire in order and the weight pieces were issued first: at tap 5 the XU x loads behind them
             // stay in flight, and tap 6's wait - its own pieces are behind them - covers them
-            if (tap == 5) CF_TAP_BARRIER(CF_XU);
+            if (tap == 5) CF_TAP_BARRIER(XU);
             else CF_TAP_BARRIER(0);                      // (tap 8: and every wave is past its last read of the chunk's x tile)
             if (tap == 6) {
 #pragma unroll
-                for (int u = 0; u < CF_XU; ++u) HK_PIN_LOADED(vx[u]);
+                for (int u = 0; u < XU; ++u) HK_PIN_LOADED(vx[u]);
             }
             if (tap == 8 && more) {
                 store_x();
@@ -505,11 +598,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
         }
     }
     if constexpr (!M32) {
-        cf16_epilogue<EPI>(acc4, sum4, ldsf, y, H, W, Cout, n, r0, c0, cot, tile, wave, tid, l15, kg, bias, mk, part);
+        cf16_epilogue<EPI, G>(acc4, sum4, ldsf, y, H, W, Cout, n, r0, c0, cot, tile, wave, tid, l15, kg, bias, mk, part);
         if (EPI != CF_EPI_POOL) return;                  // (the pooled tile is parked: it leaves below, as the other shape's)
     }
     // C layout of the 32 x 32 MFMA: column = lane & 31 (pixel), row = 8 (i / 4) + 4 (lane >> 5) + i % 4 (output channel)
-    const int row = r0 + wave, col = c0 + l31;
+    const int trow = GE::trow(true, wave, 0, l31), tcol = GE::tcol(true, 0, l31);      // (CF_MF_32: this lane's pixel of the tile)
+    const int row = r0 + trow, col = c0 + tcol;
     if (EPI == CF_EPI_NONE) {
         if (row < H && col < W) {
             float* yp = y + ((n * H + row) * W + col) * Cout + cot * CF_CO + 4 * hf;
@@ -572,25 +666,29 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
         }
     }
     if (EPI == CF_EPI_POOL) {
-        float* park = ldsf;                                          // [4 rows][32 columns][CF_PARK floats]: every wave is past the last tap's barrier
+        float* park = ldsf;                                          // [tile row][tile column][CF_PARK floats]: every wave is past the last tap's barrier
         if constexpr (M32) {
-        float* mine = park + (wave * CF_SW + l31) * CF_PARK + 4 * hf;
+        float* mine = park + (trow * GE::TW + tcol) * CF_PARK + 4 * hf;
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(mine + cb * 32 + 8 * j) = v[cb][j];
         }                                                            // (CF_MF_16: cf16_epilogue has parked the same tile)
         __syncthreads();
-        const int q = tid & 15, pc = tid >> 4;                       // channel quad, pooled column of the tile; pooled rows u = 0, 1
+        // channel quad q of pooled pixels tid / 16 and tid / 16 + 16 of the tile's TH / 2 x TW / 2, row-major (4 x 32: column tid / 16 of
+        // pooled rows u = 0, 1)
+        constexpr int TW = GE::TW, PW = TW / 2;
+        const int q = tid & 15;
         const int Ho = H / 2, Wo = W / 2;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const float* src = park + (2 * u * CF_SW + 2 * pc) * CF_PARK + 4 * q;
+            const int pp = (tid >> 4) + 16 * u, pr = pp / PW, pc = pp % PW;
+            const float* src = park + (2 * pr * TW + 2 * pc) * CF_PARK + 4 * q;
             f32x4 m = *reinterpret_cast<const f32x4*>(src);
             unsigned code = 0;
 #pragma unroll
             for (int k = 1; k < 4; ++k) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(src + ((k >> 1) * CF_SW + (k & 1)) * CF_PARK);
+                const f32x4 a = *reinterpret_cast<const f32x4*>(src + ((k >> 1) * TW + (k & 1)) * CF_PARK);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const bool take = (a[t] > m[t]) || (a[t] != a[t]);          // ATen max_pool2d: (val > max) || isnan(val)
@@ -605,7 +703,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
             unsigned c4b = (q & 2) ? (t2 | (c2 << 16)) : (c2 | (t2 << 16));
             unsigned t4 = __shfl_xor(c4b, 4);
             const unsigned long long lo = (q & 4) ? t4 : c4b, hi = (q & 4) ? c4b : t4;
-            const int ho = r0 / 2 + u, wo = c0 / 2 + pc;
+            const int ho = r0 / 2 + pr, wo = c0 / 2 + pc;
             if (ho < Ho && wo < Wo) {
                 const long long opix = (n * Ho + ho) * Wo + wo;
                 *reinterpret_cast<f32x4*>(y + opix * Cout + cot * CF_CO + 4 * q) = m;
@@ -656,6 +754,38 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __re
     }
 }
 
+// The kernel: grid xcd_grid(ntiles, Cout / 64), dynamic LDS cf_lds<MF, PLAN>().  One geometry (PLAN = CF_PLAN_4x32, CF_PLAN_8x16):
+// tile = ((n nrb + rb) nstrips + strip), rows [TH rb, ..), columns [TW strip, ..).  CF_PLAN_MIXED: tile = n tpi + t with tpi = nA + nrbB
+// nstripsB tiles an image; t < nA = nrb nstrips is tile (rb, strip) of the 8 x 16 region, whose strips are whole (nstrips = W / 16, so it may
+// be empty), the others are 16 x 8 tiles (rb, strip) of the region from column 16 nstrips on
+template <int EPI, int MF, int PLAN>
+__global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(const float* __restrict__ x, const char* __restrict__ ws,
+                                                               float* __restrict__ y, int H, int W, int Cin, int Cout, int nstrips,
+                                                               int nrb, int ntiles, const float* __restrict__ bias,
+                                                               uint8_t* __restrict__ mk, double* __restrict__ part, int nstripsB, int tpi) {
+    HK_DYN_LDS16(ldsf);
+    int tile, cot;
+    if (!xcd_map(blockIdx.x, ntiles, Cout / CF_CO, tile, cot)) return;
+    if constexpr (PLAN != CF_PLAN_MIXED) {
+        typedef CfGeo<PLAN> GE;
+        const int strip = tile % nstrips, tr = tile / nstrips;
+        const int rb = tr % nrb;
+        const long long n = tr / nrb;
+        conv3x3_split_tile<EPI, MF, PLAN>(ldsf, x, ws, y, H, W, Cin, Cout, n, rb * GE::TH, strip * GE::TW, tile, cot, bias, mk, part);
+    } else {
+        const long long n = tile / tpi;
+        const int t = tile % tpi, nA = nrb * nstrips;
+        if (t < nA) {
+            conv3x3_split_tile<EPI, MF, CF_G_8x16>(ldsf, x, ws, y, H, W, Cin, Cout, n, (t / nstrips) * 8, (t % nstrips) * 16, tile, cot, bias, mk,
+                                                   part);
+        } else {
+            const int tb = t - nA;
+            conv3x3_split_tile<EPI, MF, CF_G_16x8>(ldsf, x, ws, y, H, W, Cin, Cout, n, (tb / nstripsB) * 16, nstrips * 16 + (tb % nstripsB) * 8,
+                                                   tile, cot, bias, mk, part);
+        }
+    }
+}
+
 // part [nrows][nel] -> out [gridDim.y][nel]: group g = blockIdx.y adds rows [g rpg, (g + 1) rpg) in a fixed order, as partial_sum_kernel
 // (hk_partial_sum.h) does for all rows - the first stage (OUT = double) spreads up to 25088 partial rows (25.7 MB) over the chip, the
 // second (OUT = float) adds the groups' rows.  The column sums stay fp64 from the wave's butterfly to here and are rounded ONCE, by the
@@ -689,30 +819,66 @@ __global__ __launch_bounds__(64 * Q) void conv3x3_colsum_kernel(const double* __
     }
 }
 
+// The tiling of an H x W map on MFMA shape mf: the candidate with the fewest tiles - 4 x 32, then 8 x 16, then (CF_MF_16 only) 8 x 16 over
+// the W / 16 whole strips with 16 x 8 over the remaining columns; a tie keeps the earlier one, so nothing changes where nothing is saved.
+// Knob `conv_tile`: 0 is 4 x 32 everywhere, anything else this choice - so a launch never has more tiles than 4 x 32 gives it.
+// VGG-16 at 448 x 448: 448, 224 and 28 wide keep 4 x 32 (1568, 392 and 7 tiles an image), 112 takes 8 x 16 (98 tiles for 112), 56 the
+// mixed plan on CF_MF_16 (21 + 4 = 25 for 28) and nothing better than 28 on CF_MF_32
+struct CfPlan {
+    int plan;                                            // CF_PLAN_*
+    long long tpi;                                       // tiles of an image
+    int nrb, nstrips;                                    // the (first) region's row blocks and strips
+    int nrbB, nstripsB;                                  // CF_PLAN_MIXED: the 16 x 8 region's, from column 16 nstrips on
+};
+static CfPlan conv3x3_plan(int H, int W, int mf, int knob) {
+    auto cdiv = [](long long a, long long b) { return (int)((a + b - 1) / b); };
+    CfPlan c[3];
+    c[0] = {CF_PLAN_4x32, 0, cdiv(H, 4), cdiv(W, 32), 0, 0};
+    c[1] = {CF_PLAN_8x16, 0, cdiv(H, 8), cdiv(W, 16), 0, 0};
+    c[2] = {CF_PLAN_MIXED, 0, cdiv(H, 8), W / 16, cdiv(H, 16), cdiv(W % 16, 8)};
+    for (CfPlan& p : c) p.tpi = (long long)p.nrb * p.nstrips + (long long)p.nrbB * p.nstripsB;
+    const int ncand = mf == CF_MF_16 ? 3 : 2;
+    if (knob == 0) return c[0];
+    int best = 0;
+    for (int i = 1; i < ncand; ++i)
+        if (c[i].tpi < c[best].tpi) best = i;
+    return c[best];
+}
+
 // x [N][H][W][K] (*) w -> y [N][H][W][M] (or what EPI makes of it): the pre-pass and the main kernel; M, K multiples of 64
-template <int EPI, int MF>
+template <int EPI, int MF, int PLAN>
 static int conv3x3_run_on(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
-                          hipStream_t stream, const float* bias, uint8_t* mk, double* part) {
-    constexpr int LDS = MF == CF_MF_32 ? CF_LDS : CF16_LDS;
-    const long long nstrips = ((long long)W + CF_SW - 1) / CF_SW, nrb = ((long long)H + CF_R - 1) / CF_R, ntiles = N * nrb * nstrips;
+                          hipStream_t stream, const float* bias, uint8_t* mk, double* part, const CfPlan& pl) {
+    constexpr int LDS = cf_lds<MF, PLAN>();
+    const long long ntiles = N * pl.tpi;
     const int ncot = M / CF_CO;
     if ((ntiles + NXCD) * ncot > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
     const long long total = (long long)ncot * (K / CF_CK) * 9 * CF_CO * (MF == CF_MF_32 ? 10 : 8);
     hipLaunchKernelGGL(conv3x3_wsplit_kernel<MF>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (char*)ws, M, K,
                        transposed ? 1 : 0, total);
     HK_LAUNCH_CHECK();
-    HK_ALLOW_BIG_LDS((conv3x3_split_kernel<EPI, MF>), LDS);
-    hipLaunchKernelGGL((conv3x3_split_kernel<EPI, MF>), dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), LDS, stream, x, (const char*)ws,
-                       y, H, W, K, M, (int)nstrips, (int)nrb, (int)ntiles, bias, mk, part);
+    HK_ALLOW_BIG_LDS((conv3x3_split_kernel<EPI, MF, PLAN>), LDS);
+    hipLaunchKernelGGL((conv3x3_split_kernel<EPI, MF, PLAN>), dim3((unsigned)xcd_grid((int)ntiles, ncot)), dim3(256), LDS, stream, x,
+                       (const char*)ws, y, H, W, K, M, pl.nstrips, pl.nrb, (int)ntiles, bias, mk, part, pl.nstripsB, (int)pl.tpi);
     HK_LAUNCH_CHECK();
     return HK_OK;
 }
-// ... on the MFMA shape the knob `conv_mfma` names: 1 = 16 x 16 x 32, anything else = 32 x 32 x 16
+// the MFMA shape the knob `conv_mfma` names: 1 = 16 x 16 x 32, anything else = 32 x 32 x 16
+static int conv3x3_mf() { return tuning().conv_mfma == 1 ? CF_MF_16 : CF_MF_32; }
+// ... on that shape, tiled as conv3x3_plan says
 template <int EPI>
 static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
                        hipStream_t stream, const float* bias = nullptr, uint8_t* mk = nullptr, double* part = nullptr) {
-    if (tuning().conv_mfma == 1) return conv3x3_run_on<EPI, CF_MF_16>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part);
-    return conv3x3_run_on<EPI, CF_MF_32>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part);
+    const int mf = conv3x3_mf();
+    const CfPlan pl = conv3x3_plan(H, W, mf, tuning().conv_tile);
+    if (pl.tpi > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
+    if (mf == CF_MF_16) {
+        if (pl.plan == CF_PLAN_MIXED) return conv3x3_run_on<EPI, CF_MF_16, CF_PLAN_MIXED>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part, pl);
+        if (pl.plan == CF_PLAN_8x16) return conv3x3_run_on<EPI, CF_MF_16, CF_PLAN_8x16>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part, pl);
+        return conv3x3_run_on<EPI, CF_MF_16, CF_PLAN_4x32>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part, pl);
+    }
+    if (pl.plan == CF_PLAN_8x16) return conv3x3_run_on<EPI, CF_MF_32, CF_PLAN_8x16>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part, pl);
+    return conv3x3_run_on<EPI, CF_MF_32, CF_PLAN_4x32>(x, w, y, N, H, W, K, M, transposed, ws, stream, bias, mk, part, pl);
 }
 
 static int conv3x3_check(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
@@ -777,6 +943,22 @@ extern "C" size_t hk_conv3x3_masked_ws_bytes(int N, int H, int W, int Cin, int C
     return hk_conv3x3_ws_bytes(Cin, Cout) + (size_t)(ntiles + conv3x3_groups(ntiles)) * Cin * sizeof(double);
 }
 
+extern "C" int hk_conv3x3_tile_plan(int N, int H, int W, int mf, int* out) {
+    if (!out || N <= 0 || H <= 0 || W <= 0 || (mf != CF_MF_32 && mf != CF_MF_16)) return HK_ERR_BAD_ARG;
+    const CfPlan pl = conv3x3_plan(H, W, mf, tuning().conv_tile);
+    if (pl.tpi > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
+    const bool mixed = pl.plan == CF_PLAN_MIXED;
+    const int th = pl.plan == CF_PLAN_4x32 ? 4 : 8;
+    const bool a = pl.nstrips > 0;                                   // (the mixed plan of a map narrower than 16 has no 8 x 16 region)
+    int r[2][5] = {{th, 128 / th, pl.nrb, pl.nstrips, 0}, {16, 8, pl.nrbB, pl.nstripsB, 16 * pl.nstrips}};
+    const int first = mixed && !a ? 1 : 0, nreg = mixed && a && pl.nstripsB > 0 ? 2 : 1;
+    out[0] = (int)pl.tpi;
+    out[1] = nreg;
+    for (int i = 0; i < 2; ++i)
+        for (int k = 0; k < 5; ++k) out[2 + 5 * i + k] = i < nreg ? r[first + i][k] : 0;
+    return HK_OK;
+}
+
 extern "C" int hk_conv3x3_masked_bwd_data(const float* dy, const float* w, const uint8_t* mask, float* dx, float* dbias, int N, int H, int W,
                                           int Cin, int Cout, void* ws, size_t ws_bytes, hk_stream_t stream) {
     if (!mask || !dbias) return HK_ERR_BAD_ARG;
@@ -784,8 +966,9 @@ extern "C" int hk_conv3x3_masked_bwd_data(const float* dy, const float* w, const
     if (rc != HK_OK) return rc;
     if (ws_bytes < hk_conv3x3_masked_ws_bytes(N, H, W, Cin, Cout)) return HK_ERR_WORKSPACE;
     if (!aligned16(mask) || tuning().conv_epi < 2) return HK_ERR_UNSUPPORTED;
-    const long long ntiles = conv3x3_tiles(N, H, W), ngroups = conv3x3_groups(ntiles);
-    if (ntiles > 0x7fffffffll || ngroups > 65535) return HK_ERR_UNSUPPORTED;
+    // the partial rows are those of the tiles the launch really has: never more than the 4 x 32 tiles the workspace is sized for
+    const long long ntiles = N * conv3x3_plan(H, W, conv3x3_mf(), tuning().conv_tile).tpi, ngroups = conv3x3_groups(ntiles);
+    if (ntiles > conv3x3_tiles(N, H, W) || ntiles > 0x7fffffffll || ngroups > 65535) return HK_ERR_UNSUPPORTED;
     double* part = reinterpret_cast<double*>((char*)ws + hk_conv3x3_ws_bytes(Cin, Cout));    // [ntiles][Cin], then [ngroups][Cin]
     double* grp = part + ntiles * Cin;
     const int rc2 = conv3x3_run<CF_EPI_MASK>(dy, w, dx, N, H, W, Cout, Cin, true, ws, (hipStream_t)stream, nullptr, const_cast<uint8_t*>(mask), part);

@@ -75,6 +75,8 @@ struct Tuning {
     int conv_mfma = -1;     // HK_CONV_MFMA     bf16 MFMA of those kernels (conv_fwd.hip, MF): 1: v_mfma_f32_16x16x32_bf16, 0: v_mfma_f32_32x32x16_bf16, -1: the
                             //                  caller's choice per call - the Python layer sets 1 around the calls of its measured table
                             //                  (functional.CONV_MFMA16_FWD / CONV_MFMA16_BWD_DATA), anybody else gets 32x32x16
+    int conv_tile = -1;     // HK_CONV_TILE     which 128 pixels a workgroup of those kernels takes (conv_fwd.hip, G): -1: per map and MFMA shape the tiling with
+                            //                  the fewest tiles (conv3x3_plan: 4 x 32, 8 x 16, or 8 x 16 with a 16 x 8 remainder strip), 0: 4 x 32 everywhere
     int peer_form = 0;      // HK_PEER_FORM     hk_peer_loss: 0: automatic - the one-launch LDS-resident form wherever both logit matrices fit one
                             //                  workgroup's LDS (by launch count: NOT yet timed on the device), 1: the three-launch general form,
                             //                  2: the resident form or HK_ERR_UNSUPPORTED

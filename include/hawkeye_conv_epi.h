@@ -21,7 +21,7 @@ extern "C" {
  *   hk_conv3x3_masked_bwd_data     dx [N][H][W][Cin] = the plain input gradient where the bit of `mask` ([N][H][W][Cin/4], 16-byte aligned:
  *                                  the sign mask of the map x, written by the layer that produced it) is set, else 0 - the bits of the
  *                                  plain input gradient followed by hk_bias_relu_bwd - and dbias [Cin] = the column sums of dx, i.e. the
- *                                  PRODUCING layer's bias gradient: one partial row per 4 x 32-pixel tile, added in a fixed order in two
+ *                                  PRODUCING layer's bias gradient: one partial row per 128-pixel tile (hawkeye_conv_tile.h), added in a fixed order in two
  *                                  stages (no atomics, the same bits every run; another order than hk_bias_relu_bwd's, so dbias agrees
  *                                  with it to rounding only).  Workspace hk_conv3x3_masked_ws_bytes(N, H, W, Cin, Cout): the split
  *                                  weights and the partial rows

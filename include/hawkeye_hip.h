@@ -82,6 +82,8 @@ const char* hk_version(void);
  *   "conv_mfma"     the bf16 MFMA those kernels run on: 1 = v_mfma_f32_16x16x32_bf16, 0 = v_mfma_f32_32x32x16_bf16, -1 (default) = per
  *                   call: 32x32x16 unless the caller has set 1 for the call, as the Python layer does for the layers of its
  *                   measured table.  Same results to the bound of hawkeye_conv.h either way; the bits differ
+ *   "conv_tile"     which 128 pixels a workgroup of those kernels takes: -1 (default) = per map and MFMA shape the tiling with the fewest
+ *                   tiles (hk_conv3x3_tile_plan), 0 = 4 rows x 32 columns everywhere.  The same bits either way
  * Values are seeded once from the environment (HK_<NAME>) when the library is first used; the launch paths never read
  * the environment.  Returns HK_ERR_BAD_ARG for an unknown name.  Process-wide: set them only while no other thread is
  * launching. */
@@ -674,6 +676,7 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 
 #include "hawkeye_conv.h" /* the trunk's forward and input gradient */
 #include "hawkeye_conv_epi.h" /* ... with the trunk's epilogue passes done inside those kernels */
+#include "hawkeye_conv_tile.h" /* ... and how those kernels tile a map */
 #include "hawkeye_interp.h" /* the InterpParts plugin: region grouping and the shaping loss */
 
 #endif /* HAWKEYE_HIP_H */
