@@ -158,12 +158,22 @@ INTERP_SIGNATURES = {
     'hk_ip_loss': (c_i, [c_f] * 5 + [c_fl] + [c_f] * 3 + [c_i] * 6 + [c_f, c_sz, c_f]),
 }
 
+# the MGE-CNN plugin's part pool, Grad-CAM box and criterion; mirrors include/hawkeye_mge.h one to one
+MGE_SIGNATURES = {
+    'hk_mge_partpool_fwd_ws_bytes': (c_sz, [c_i] * 5),
+    'hk_mge_partpool_fwd': (c_i, [c_f] * 5 + [c_i] * 5 + [c_f, c_sz, c_f]),
+    'hk_mge_partpool_bwd': (c_i, [c_f] * 6 + [c_i] * 5 + [c_f]),
+    'hk_mge_cam_bbox': (c_i, [c_f] * 4 + [c_i] * 5 + [c_fl, c_i, c_f]),
+    'hk_mge_loss_ws_bytes': (c_sz, [c_i, c_i]),
+    'hk_mge_loss': (c_i, [c_f, c_f, c_fl, c_f, c_f, c_i, c_i, c_i, c_f, c_sz, c_f]),     # (1st and 5th: HOST arrays of K device pointers)
+}
+
 
 def attach(lib):
-    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES, TRUNK_TILE_SIGNATURES and INTERP_SIGNATURES its
+    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES, TRUNK_TILE_SIGNATURES, INTERP_SIGNATURES and MGE_SIGNATURES its
     prototype on a library object (the gfx950 build, or whatever stands in for it).  Returns the library."""
     for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()) + list(TRUNK_EPI_SIGNATURES.items()) + \
-            list(TRUNK_TILE_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
+            list(TRUNK_TILE_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + list(MGE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args

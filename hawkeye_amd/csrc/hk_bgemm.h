@@ -193,6 +193,15 @@ struct EpAffine {
     }
 };
 
+// An epilogue with a member type `Tile` takes the workgroup's whole 64 x 64 tile instead of single elements:
+//   void tile(int b, int tm, int tn, int tilesN, int M, int N, const f32x16& acc, float* lds)
+// called by every thread with its wave's accumulator (C/D layout below) and the free LDS stages (at least 2 x 64 x 2 floats
+// are used by the one user, the MGE-CNN part pool's row maximum in mge.hip).  Other epilogues compile as before.
+template <class EP, class = void>
+struct EpTakesTile : std::false_type {};
+template <class EP>
+struct EpTakesTile<EP, std::void_t<typename EP::Tile>> : std::true_type {};
+
 // ---------------------------------------------------------------- kernel
 // 64x64 workgroup tile (4 waves x one 32x32 accumulator split into two k-chains, 37 KB LDS, 4 workgroups / CU), K in
 // chunks of 32.  Round 1 also carried a 128x128 tile, 64- and 16-deep chunks, a two-chunk prefetch, a symmetric-tile
@@ -379,6 +388,11 @@ __global__ __launch_bounds__(256) void bgemm_kernel(AL al, BL bl, EP ep, int M, 
 #undef HK_SSTORE_FROM
 
     if (T == 1) acc[0][0] += acc2;
+    if constexpr (EpTakesTile<EP>::value) {
+        // (the last chunk's barrier has passed: the stages are free) the epilogue reduces the tile itself
+        ep.tile(b, tm, tn, tilesN, M, N, acc[0][0], lds);
+        return;
+    }
     if constexpr (VEPI) {
         // (the last chunk's barrier has passed: the stages are free) tile image [64][68], then 16 float4 per row
         static_assert(T == 1 && 64 * 68 <= 2 * (SA + SB), "the output image fits the stages");

@@ -1667,6 +1667,156 @@ def ip_loss(logits, assign, labels, radius=2, std=0.4, alpha=1.0, beta=0.001, co
     return ip_loss_with_terms(logits, assign, labels, radius, std, alpha, beta, coeff, window, prior)[0]
 
 
+# --------------------------------------------------------------------- MGE-CNN part pool, Grad-CAM box, loss
+MGE_MAX_LOGITS = 16
+
+
+def _mge_partpool_args(x, weight, bias, what):
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise _lib.HawkeyeHipError(f'{what}: x must be [B, Cin, H, W], got {tuple(x.shape)}')
+    cin = x.shape[1]
+    if cin % 32:
+        raise _lib.HawkeyeHipError(f'{what}: Cin must be a multiple of 32, got {cin}')
+    if weight.dim() not in (2, 4) or weight.shape[0] < 1 or weight.numel() != weight.shape[0] * cin:
+        raise _lib.HawkeyeHipError(f'{what}: weight must be [Cout, {cin}] or [Cout, {cin}, 1, 1], got {tuple(weight.shape)}')
+    cout = weight.shape[0]
+    if tuple(bias.shape) != (cout,):
+        raise _lib.HawkeyeHipError(f'{what}: bias must hold {cout} values, got {tuple(bias.shape)}')
+    _one_device(what, x.device, weight, bias)
+    return _f32c(x), _f32c(weight).reshape(cout, cin), _f32c(bias)
+
+
+def mge_partpool_fwd(x, weight, bias):
+    """The raw forward (hk_mge_partpool_fwd): -> (pooled [B,Cout], argmax int32 [B,Cout]).  No autograd."""
+    x, weight, bias = _mge_partpool_args(x.detach(), weight.detach(), bias.detach(), 'mge_partpool')
+    lib = _lib.load()
+    b, cin, h, w = x.shape
+    cout = weight.shape[0]
+    pooled = torch.empty(b, cout, dtype=torch.float32, device=x.device)
+    argmax = torch.empty(b, cout, dtype=torch.int32, device=x.device)
+    nws = lib.hk_mge_partpool_fwd_ws_bytes(b, cin, cout, h, w)
+    ws = _ws(nws, x.device)
+    check(lib.hk_mge_partpool_fwd(ptr(x), ptr(weight), ptr(bias), ptr(pooled), ptr(argmax), b, cin, cout, h, w, ptr(ws), nws, stream()),
+          'hk_mge_partpool_fwd')
+    return pooled, argmax
+
+
+def mge_partpool_bwd(x, g, pooled, argmax, need=(True, True)):
+    """The raw backward (hk_mge_partpool_bwd): x [B,Cin,H,W], g and pooled [B,Cout], argmax int32 [B,Cout] -> (dw [Cout,Cin],
+    db [Cout]), None where `need` says so.  No autograd."""
+    lib = _lib.load()
+    x = _f32c(x)
+    b, cin, h, w = x.shape
+    cout = pooled.shape[1]
+    g, pooled = _f32_shaped(g, (b, cout), 'mge_partpool_bwd', 'g'), _f32_shaped(pooled, (b, cout), 'mge_partpool_bwd', 'pooled')
+    argmax = _int_tensor(argmax, (b, cout), torch.int32, x.device, 'mge_partpool_bwd', 'argmax', same_device=True)
+    dw = torch.empty(cout, cin, dtype=torch.float32, device=x.device) if need[0] else None
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if need[1] else None
+    check(lib.hk_mge_partpool_bwd(ptr(x), ptr(g), ptr(pooled), ptr(argmax), ptr(dw), ptr(db), b, cin, cout, h, w, stream()),
+          'hk_mge_partpool_bwd')
+    return dw, db
+
+
+class _MGEPartPool(torch.autograd.Function):
+    """replaces pool_max(relu(conv6(x.detach()))) of LocalCamNet.forward, model/methods/MGE_CNN/MGE.py:135,166,197."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.wshape = weight.shape
+        pooled, argmax = mge_partpool_fwd(x, weight, bias)
+        ctx.save_for_backward(x, pooled, argmax)
+        ctx.mark_non_differentiable(argmax)
+        return pooled, argmax
+
+    @staticmethod
+    def backward(ctx, g, _g_argmax):
+        x, pooled, argmax = ctx.saved_tensors
+        dw, db = mge_partpool_bwd(x, g, pooled, argmax, ctx.needs_input_grad[1:])
+        return None, None if dw is None else dw.view(ctx.wshape), db
+
+
+def mge_partpool(x, weight, bias):
+    """MGE-CNN's part pool: x [B,Cin,H,W] (no gradient reaches it: the reference detaches it), weight [Cout,Cin] or
+    [Cout,Cin,1,1] and bias [Cout] of a Conv2d(Cin, Cout, 1, 1, padding=1) -> [B,Cout] = the global maximum of relu(conv(x)) over
+    the padded (H + 2) x (W + 2) map, which is never written.  One autograd node; its backward is a gather of one pixel per
+    (image, channel).  Cin a multiple of 32."""
+    return _MGEPartPool.apply(x, weight, bias)[0]
+
+
+def mge_cam_weights(cls_weight, index, hw):
+    """The Grad-CAM channel weights in closed form: relu(W[index]) / hw [B,C] - what the reference's autograd run through the last
+    block, AdaptiveAvgPool2d(1) and the classifier returns (grad_cam.py:82-86).  Plain torch ops; hk_mge_cam_bbox does the same inside."""
+    return torch.relu(cls_weight.detach()[index.long()]) / float(hw)
+
+
+def mge_cam_bbox(conv5, cls_weight, index, rate, image_size):
+    """conv5 [B,C,h,w], cls_weight [classes,C], index integer [B] on the device -> boxes int32 [B,1,4] = y0, x0, y1, x1 (exclusive
+    ends) of the region whose normalised, bilinearly upsampled (align_corners) class activation map is >= rate, as get_bbox
+    (MGE.py:48-72) slices it; the whole image 0, 0, S, S where that slice is empty, the map is constant or `index` is out of
+    range.  No autograd, no host round trip; feed the boxes to nts_crop_resize(images, boxes, 0, S)."""
+    what = 'mge_cam_bbox'
+    if conv5.dim() != 4 or min(conv5.shape) < 1:
+        raise _lib.HawkeyeHipError(f'{what}: conv5 must be [B, C, h, w], got {tuple(conv5.shape)}')
+    conv5 = _f32c(conv5.detach())
+    b, c, h, w = conv5.shape
+    if cls_weight.dim() != 2 or cls_weight.shape[1] != c or cls_weight.shape[0] < 1:
+        raise _lib.HawkeyeHipError(f'{what}: cls_weight must be [classes, {c}], got {tuple(cls_weight.shape)}')
+    _one_device(what, conv5.device, cls_weight)
+    cls_weight = _f32c(cls_weight.detach())
+    index = _int_tensor(index, (b,), torch.int32, conv5.device, what, 'index', same_device=True)
+    s = int(image_size)
+    if h * w > 512 or not 1 <= s <= 2048:
+        raise _lib.HawkeyeHipError(f'{what}: a map of at most 512 pixels and an image side of 1 .. 2048 are served, got {h} x {w} and {s}')
+    lib = _lib.load()
+    boxes = torch.empty(b, 1, 4, dtype=torch.int32, device=conv5.device)
+    check(lib.hk_mge_cam_bbox(ptr(conv5), ptr(cls_weight), ptr(index), ptr(boxes), b, c, h, w, cls_weight.shape[0], float(rate), s,
+                              stream()), 'hk_mge_cam_bbox')
+    return boxes
+
+
+class _MGELoss(torch.autograd.Function):
+    """replaces the ten criterion calls and their mean, Examples/MGE_CNN.py:43-45: the mean, the K terms and the K gradients of
+    the mean from one launch; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, labels, label_smoothing, *logits):
+        import ctypes
+        lib = _lib.load()
+        k = len(logits)
+        b, c = logits[0].shape
+        grads = [torch.empty_like(t) for t in logits]
+        loss = torch.empty(1 + k, dtype=torch.float32, device=logits[0].device)
+        table = ctypes.c_void_p * k
+        nws = lib.hk_mge_loss_ws_bytes(k, b)
+        ws = _ws(nws, logits[0].device)
+        check(lib.hk_mge_loss(table(*[ptr(t).value for t in logits]), ptr(labels), label_smoothing, ptr(loss),
+                              table(*[ptr(t).value for t in grads]), k, b, c, ptr(ws), nws, stream()), 'hk_mge_loss')
+        return _loss_forward(ctx, loss, grads)
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        return (None, None) + _loss_backward(ctx, g, 0)
+
+
+def mge_loss_with_terms(logits, labels, label_smoothing=0.1):
+    """MGE-CNN's criterion on a list of K <= 16 logits tensors [B,C] (the model's ten) and labels [B] -> (the mean of the K
+    label-smoothed cross entropies, the device tensor of the K terms, not differentiable).  One launch for the loss and every
+    gradient; the reference calls CrossEntropyLoss once per tensor."""
+    what = 'mge_loss'
+    logits = list(logits)
+    if not 1 <= len(logits) <= MGE_MAX_LOGITS:
+        raise _lib.HawkeyeHipError(f'{what}: 1 .. {MGE_MAX_LOGITS} logits tensors are served, got {len(logits)}')
+    if logits[0].dim() != 2 or min(logits[0].shape) < 1 or any(t.shape != logits[0].shape for t in logits):
+        raise _lib.HawkeyeHipError(f'{what}: every logits tensor must be [B, C] of one shape, got {[tuple(t.shape) for t in logits]}')
+    _one_device(what, logits[0].device, *logits)
+    y = _int_tensor(labels, (logits[0].shape[0],), torch.int32, logits[0].device, what, 'labels')
+    return _MGELoss.apply(y, float(label_smoothing), *[_f32c(t) for t in logits])
+
+
+def mge_loss(logits, labels, label_smoothing=0.1):
+    return mge_loss_with_terms(logits, labels, label_smoothing)[0]
+
+
 # --------------------------------------------------------------------- classifier
 class _Linear(torch.autograd.Function):
     """replaces nn.Linear on the pooled vector (model/methods/BCNN.py:42,54 and the other heads' classifiers)."""

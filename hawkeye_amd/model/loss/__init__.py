@@ -6,3 +6,4 @@ from .NTS_loss import NTSLoss  # noqa: F401
 from .CrossX_loss import CrossXLoss  # noqa: F401
 from .DCL_loss import DCLLoss  # noqa: F401
 from .InterpParts_loss import InterpPartsLoss  # noqa: F401
+from .MGE_loss import MGELoss  # noqa: F401

@@ -678,5 +678,6 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 #include "hawkeye_conv_epi.h" /* ... with the trunk's epilogue passes done inside those kernels */
 #include "hawkeye_conv_tile.h" /* ... and how those kernels tile a map */
 #include "hawkeye_interp.h" /* the InterpParts plugin: region grouping and the shaping loss */
+#include "hawkeye_mge.h" /* the MGE-CNN plugin: part pool, Grad-CAM box and the criterion */
 
 #endif /* HAWKEYE_HIP_H */
