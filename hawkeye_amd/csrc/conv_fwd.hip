@@ -59,7 +59,7 @@
 //              every pixel offset, 63744 B).  Measured at batch 64 ("The MFMA shape"): 196 - 227 TF/s stand-alone where the
 //              other shape gives 177 - 205; in the step the 24 launches 70.2 ms against 80.2 with every layer on it; per launch 9 - 11 %
 //              fewer cycles (LDS bank conflicts 7 % -> 0, a fifth less weight traffic) at a 3 - 4 % higher clock, the matrix pipe
-//              61 - 72 % busy.  Routed per layer, direction and batch by functional.py's measured table.  Registers
+//              61 - 72 % busy.  Which shape a call runs on is decided here (conv3x3_mfma16_wins: every call on 16 x 16 x 32).  Registers
 //              with the weight tiles by DMA and every fragment read in front of the MFMAs: 204 - 206 VGPRs (MF = 0: 190 - 192), no spill
 //              (8 x 16: 200 - 202 and 184 - 188; the launch with both 8 x 16 and 16 x 8: 206 - 208)
 #include "hk_common.h"
@@ -863,13 +863,29 @@ static int conv3x3_run_on(const float* x, const float* w, float* y, int N, int H
     HK_LAUNCH_CHECK();
     return HK_OK;
 }
-// the MFMA shape the knob `conv_mfma` names: 1 = 16 x 16 x 32, anything else = 32 x 32 x 16
-static int conv3x3_mf() { return tuning().conv_mfma == 1 ? CF_MF_16 : CF_MF_32; }
+// Whether the GEMM of a call - x [N][H][W][K] (*) w -> [N][H][W][M], for the input gradient K = Cout and M = Cin: the forward of dy - is
+// faster on v_mfma_f32_16x16x32_bf16: what knob `conv_mfma` runs at its default.  A function of the GEMM alone: the four epilogues of one
+// GEMM run one main loop, and an input gradient runs the loop that the forward of dy with flipped weights runs.
+// Rule: always.  Measured on an MI355X inside the training step (VGG-16 at 448 x 448, HK_CONV_MFMA=0 against the default, one kernel trace
+// each: profiles/conv_mf16_step_layers.json): all 24 layer-directions are faster on 16 x 16 x 32 at batch 64 (0.16 - 1.21 ms a launch, the 24
+// launches 75.3 -> 62.2 ms) and at batch 16 (19.0 -> 16.0), as all 48 were before the planned tiles (profiles/conv_wdma_mfma_step_layers.json);
+// the stand-alone bar that functional.py's tables were made with decides by its own noise ("Weight tiles by LDS-DMA", last
+// paragraph).  The arguments are what a finer rule would be written in
+static bool conv3x3_mfma16_wins(int N, int H, int W, int K, int M) {
+    (void)N, (void)H, (void)W, (void)K, (void)M;
+    return true;
+}
+// THE MFMA shape of a call, for everything that follows it (the plan's geometries, the pre-pass, the main kernel, the partial rows of the
+// masked input gradient): knob `conv_mfma` 1 = 16 x 16 x 32 everywhere, 0 = 32 x 32 x 16 everywhere, -1 (the default) = the rule above
+static int conv3x3_mf(int N, int H, int W, int K, int M) {
+    const int knob = tuning().conv_mfma;
+    return knob == 1 || (knob < 0 && conv3x3_mfma16_wins(N, H, W, K, M)) ? CF_MF_16 : CF_MF_32;
+}
 // ... on that shape, tiled as conv3x3_plan says
 template <int EPI>
 static int conv3x3_run(const float* x, const float* w, float* y, int N, int H, int W, int K, int M, bool transposed, void* ws,
                        hipStream_t stream, const float* bias = nullptr, uint8_t* mk = nullptr, double* part = nullptr) {
-    const int mf = conv3x3_mf();
+    const int mf = conv3x3_mf(N, H, W, K, M);
     const CfPlan pl = conv3x3_plan(H, W, mf, tuning().conv_tile);
     if (pl.tpi > 0x7fffffffll) return HK_ERR_UNSUPPORTED;
     if (mf == CF_MF_16) {
@@ -966,8 +982,9 @@ extern "C" int hk_conv3x3_masked_bwd_data(const float* dy, const float* w, const
     if (rc != HK_OK) return rc;
     if (ws_bytes < hk_conv3x3_masked_ws_bytes(N, H, W, Cin, Cout)) return HK_ERR_WORKSPACE;
     if (!aligned16(mask) || tuning().conv_epi < 2) return HK_ERR_UNSUPPORTED;
-    // the partial rows are those of the tiles the launch really has: never more than the 4 x 32 tiles the workspace is sized for
-    const long long ntiles = N * conv3x3_plan(H, W, conv3x3_mf(), tuning().conv_tile).tpi, ngroups = conv3x3_groups(ntiles);
+    // the partial rows are those of the tiles the launch really has (the GEMM is the forward of dy: K = Cout, M = Cin): never more than the
+    // 4 x 32 tiles the workspace is sized for
+    const long long ntiles = N * conv3x3_plan(H, W, conv3x3_mf(N, H, W, Cout, Cin), tuning().conv_tile).tpi, ngroups = conv3x3_groups(ntiles);
     if (ntiles > conv3x3_tiles(N, H, W) || ntiles > 0x7fffffffll || ngroups > 65535) return HK_ERR_UNSUPPORTED;
     double* part = reinterpret_cast<double*>((char*)ws + hk_conv3x3_ws_bytes(Cin, Cout));    // [ntiles][Cin], then [ngroups][Cin]
     double* grp = part + ntiles * Cin;

@@ -37,8 +37,8 @@ namespace hk {
 
 // A/B levers for tests, benchmarks and profiling (hk_tuning_set / hk_tuning_get in the C ABI).  The values are seeded
 // from the environment ONCE, when the library is first used; the launch paths read plain ints - no getenv per call.
-// The product never sets them: every default is the measured winner (one exception, conv_mfma: its default hands the choice to the
-// caller, and the Python layer passes its measured table's choice through the knob for the length of a call).
+// The product never has to set them: every default is the measured winner (the Python layer still sets conv_mfma to 1 for the length of
+// the calls of its older measured table - a subset of what the default now chooses anyway: conv_fwd.hip, conv3x3_mfma16_wins).
 struct Tuning {
     int bcnn_generic = 0;   // HK_BCNN_GENERIC  1: generic GEMM path instead of the panel-resident Gram / backward kernels
     int cbp_bin = -1;       // HK_CBP_BIN      -1: by batch size, 0: row-sketch, 1: CSR gather, 2: row-scatter
@@ -72,9 +72,9 @@ struct Tuning {
     int conv_epi = 2;       // HK_CONV_EPI      epilogues of those kernels (conv_fwd.hip, EPI): 0: none - bias, ReLU, pool and the ReLU backward stay the
                             //                  passes of trunk.hip, 1: bias + ReLU (+ pool) inside the forward, 2: and the producer's sign mask and
                             //                  bias-gradient partials inside the input gradient (the entry points refuse below their level)
-    int conv_mfma = -1;     // HK_CONV_MFMA     bf16 MFMA of those kernels (conv_fwd.hip, MF): 1: v_mfma_f32_16x16x32_bf16, 0: v_mfma_f32_32x32x16_bf16, -1: the
-                            //                  caller's choice per call - the Python layer sets 1 around the calls of its measured table
-                            //                  (functional.CONV_MFMA16_FWD / CONV_MFMA16_BWD_DATA), anybody else gets 32x32x16
+    int conv_mfma = -1;     // HK_CONV_MFMA     bf16 MFMA of those kernels (conv_fwd.hip, MF): 1: v_mfma_f32_16x16x32_bf16, 0: v_mfma_f32_32x32x16_bf16,
+                            //                  -1: per call, the measured winner (conv_fwd.hip: conv3x3_mfma16_wins - a function of the GEMM's shape alone,
+                            //                  the same for every epilogue and for an input gradient as for the forward of dy)
     int conv_tile = -1;     // HK_CONV_TILE     which 128 pixels a workgroup of those kernels takes (conv_fwd.hip, G): -1: per map and MFMA shape the tiling with
                             //                  the fewest tiles (conv3x3_plan: 4 x 32, 8 x 16, or 8 x 16 with a 16 x 8 remainder strip), 0: 4 x 32 everywhere
     int peer_form = 0;      // HK_PEER_FORM     hk_peer_loss: 0: automatic - the one-launch LDS-resident form wherever both logit matrices fit one

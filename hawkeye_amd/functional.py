@@ -2323,6 +2323,7 @@ def conv3x3_bwd_data_ok(x, conv):
 # bar (profiles/conv_mfma_timing.json: the 32 x 32 x 16 arm's fastest repeat minus the 16 x 16 x 32 arm's slowest more than three times
 # the 32 x 32 x 16 arm's own spread) AND was faster inside the training step (profiles/conv_mfma_step_layers.json; DESIGN 3.10, "The
 # MFMA shape").  Nothing that was not measured is here; a shape or batch that is not listed keeps 32 x 32 x 16.
+# (Since the library chooses the shape itself at -1 - csrc/conv_fwd.hip, conv3x3_mfma16_wins: always 16 x 16 x 32 - these tables are a subset of what it does anyway.)
 CONV_MFMA16_FWD = {
     (256, 256, 112, 112): (64,),                                                                       # conv3_2 / conv3_3
     (256, 512, 56, 56): (64, 16), (512, 512, 56, 56): (64,),                                           # conv4_1, conv4_2 / conv4_3
