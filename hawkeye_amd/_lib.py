@@ -148,6 +148,13 @@ TRUNK_TILE_SIGNATURES = {
     'hk_conv3x3_tile_plan': (c_i, [c_i, c_i, c_i, c_i, c_f]),     # (5th: int[12] on the HOST)
 }
 
+# ... and the weight gradient of the trunk's pooled layers from the pooled gradient (knob `wrw_pool`); mirrors include/hawkeye_conv_pool.h
+TRUNK_POOL_SIGNATURES = {
+    'hk_conv3x3_wrw_pooled': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_sz, c_f]),
+    'hk_conv3x3_wrw_pooled_served': (c_i, [c_i] * 5),
+    'hk_conv3x3_wrw_pooled_plan': (c_i, [c_i] * 5 + [c_f]),     # (6th: int[5] on the HOST)
+}
+
 # the InterpParts plugin's grouping unit and criterion; mirrors include/hawkeye_interp.h one to one
 INTERP_SIGNATURES = {
     'hk_ip_group_fwd_ws_bytes': (c_sz, [c_i] * 5),
@@ -170,10 +177,10 @@ MGE_SIGNATURES = {
 
 
 def attach(lib):
-    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES, TRUNK_TILE_SIGNATURES, INTERP_SIGNATURES and MGE_SIGNATURES its
+    """Give every function of SIGNATURES, TRUNK_SIGNATURES, TRUNK_EPI_SIGNATURES, TRUNK_TILE_SIGNATURES, TRUNK_POOL_SIGNATURES, INTERP_SIGNATURES and MGE_SIGNATURES its
     prototype on a library object (the gfx950 build, or whatever stands in for it).  Returns the library."""
     for name, (res, args) in list(SIGNATURES.items()) + list(TRUNK_SIGNATURES.items()) + list(TRUNK_EPI_SIGNATURES.items()) + \
-            list(TRUNK_TILE_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + list(MGE_SIGNATURES.items()):
+            list(TRUNK_TILE_SIGNATURES.items()) + list(TRUNK_POOL_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + list(MGE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError => header/library drifted apart
         fn.restype = res
         fn.argtypes = args

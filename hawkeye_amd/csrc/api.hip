@@ -26,6 +26,7 @@ const Knob kKnobs[] = {
     {"conv_fwd", "HK_CONV_FWD", &Tuning::conv_fwd},             {"conv_bwd_data", "HK_CONV_BWD_DATA", &Tuning::conv_bwd_data},
     {"conv_epi", "HK_CONV_EPI", &Tuning::conv_epi},             {"conv_mfma", "HK_CONV_MFMA", &Tuning::conv_mfma},
     {"wrw_mfma", "HK_WRW_MFMA", &Tuning::wrw_mfma},             {"conv_tile", "HK_CONV_TILE", &Tuning::conv_tile},
+    {"wrw_pool", "HK_WRW_POOL", &Tuning::wrw_pool},
 };
 Tuning from_env() {
     Tuning t;

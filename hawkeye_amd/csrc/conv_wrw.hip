@@ -85,11 +85,36 @@
 //              107.5 ms.  The rule behind the knob's default is therefore "always" (wrw_mfma16_wins).  The split and
 //              the LDS stores moved in between the MFMAs (no serial tail) took 2.6 % of the cycles and gave most of it back in clock:
 //              0.7 ms of the step, inside the bar - not kept
+//
+// Pooled (conv3x3_wrw_pooled_kernel, hk_conv3x3_wrw_pooled, knob wrw_pool): five of the twelve routed layers end in a 2 x 2 max-pool, and
+// the dy that bias_relu_pool_bwd_kernel hands their weight gradient is three quarters zeros by construction: one value per window and
+// channel, at the argmax.  Along a row every aligned group of four pixels is two window halves - at most two non-zeros, the first at
+// position 0 or 1 and the second at 2 or 3: the 2:4 pattern of v_smfmac_f32_16x16x64_bf16 (hk_smfmac_bf16.h), which covers K = 64 in
+// the time v_mfma_f32_16x16x32_bf16 covers 32.  The kernel takes the pooled gradient dp, the pooled output p (ReLU's mask) and the
+// forward's argmax codes, never reads dy, and issues half the matrix instructions.
+//   step     = one window row = two image rows; K = 64 is the strip's 32 pixels of row r, then of row r + 1 (wrp_krow, wrp_kpix), so
+//              a B operand is the dense form's x fragments of two ring slots one after the other and a row's fragment serves two taps
+//   dy       = per window row 16 windows x 64 channels of masked dp, split into the three pieces, and the codes as 16 bits a channel:
+//              planes of [17 windows][16 channels] (wrp_aoff), 8704 B, ONE buffer - a lane's eight kept values are the eight windows
+//              under its sixteen pixels (two transposing reads a plane), zeroed where the code's row bit is not the lane's row, at
+//              position 2 (window % 2) + the code's column bit; fragments and index are formed once per step for its 216 MFMAs
+//   ring     = FIVE x slots (67200 B): row r + 3 goes into the free slot half way through the step's MFMAs; row r + 4 and the next dy
+//              behind a barrier after them: two barriers per two rows.  Row blocks start on even rows (wrw_plan, `even`)
+//   limits   = LDS 75904 B (dynamic): two workgroups per CU.  The "no scratch, no spill" the dense kernels keep is MISSED (kernel-resource-usage):
+//              wide 256 VGPRs, 16 bytes of scratch a lane, 3 VGPRs and 9 SGPRs spilled (the SGPRs into the lanes of v255); Cin 64 256 VGPRs, 12
+//              bytes, 2 VGPRs, no SGPR.  The spill stores stand in front of the job loop, the reloads at the head of a job (no untracked load is
+//              in flight there), none in the step loop.  Loads through a scalar base took it from 29 spilled VGPRs; five further attempts did
+//              not improve it
+//   measured = the sparse instruction issues in 0.95 x the dense one's time (profiles/wrw_pool_probe.json).  Inside the training step all five layers
+//              0.65 - 0.68 x the dense kernel's time at batch 64 (16.07 -> 10.69 ms together) and 0.36 - 0.68 x at batch 16
+//              (profiles/wrw_pool_step_layers.json); the step 98.99 -> 94.01 ms at batch 64, 27.03 -> 24.85 at 16
 #include "hk_common.h"
 #include "hk_partial_sum.h"
 #include "hk_split_bf16.h"
 #include <hk_mfma_bf16.h>   // the 16 x 16 x 32 bf16 MFMA (the emulation build finds its model of it first)
+#include <hk_smfmac_bf16.h> // the 2:4 sparse 16 x 16 x 64 bf16 MFMA (likewise)
 #include "../../include/hawkeye_hip.h"
+#include "../../include/hawkeye_conv_pool.h"
 
 namespace hk {
 
@@ -683,7 +708,8 @@ struct WrwPlan {
 // workgroups per CU over all slices
 static int wrw_wide_wgs(long long slices) { return slices < 512 ? (int)(512 / slices) : 1; }
 
-static bool wrw_plan(int N, int H, int W, int slices, bool wide, WrwPlan& pl) {
+// (even: row blocks start on even rows - the pooled form's two-row steps, "Pooled" below; H is even there)
+static bool wrw_plan(int N, int H, int W, int slices, bool wide, WrwPlan& pl, bool even = false) {
     // two workgroups per CU over all slices (two waves per SIMD cover each other's LDS waits: conv1_2 6.54 ms against 6.72 with one)
     const int room = wide ? wrw_wide_wgs(slices) : WRW_MAX_WG;
     int wgmax = tuning().wrw_wgs > 0 ? tuning().wrw_wgs : (wide ? room : (slices <= 8 ? 512 / slices : 64));
@@ -691,7 +717,7 @@ static bool wrw_plan(int N, int H, int W, int slices, bool wide, WrwPlan& pl) {
     const long long nstrips = ((long long)W + WRW_SW - 1) / WRW_SW, base = (long long)N * nstrips;
     long long best = -1;
     for (int cand = 1; cand <= (H / WRW_MIN_ROWS > 1 ? H / WRW_MIN_ROWS : 1); ++cand) {
-        const int rpb = (H + cand - 1) / cand, nrb = (H + rpb - 1) / rpb;
+        const int rpb = (H + cand - 1) / cand + (even ? ((H + cand - 1) / cand) & 1 : 0), nrb = (H + rpb - 1) / rpb;
         if (nrb != cand) continue;
         const long long jobs = base * nrb;
         if (jobs > 0x7fffffffll) break;
@@ -715,6 +741,346 @@ static int wrw_split_launch(dim3 grid, const float* dy, const float* x, float* p
                        pl.nrb, pl.rpb, pl.njobs, cin);
     HK_LAUNCH_CHECK();
     return HK_OK;
+}
+
+// ---- Pooled: the weight gradient of a layer that ends in a 2 x 2 max-pool, on the 2:4 sparse MFMA (header: "Pooled") ----
+constexpr int WRP_SLOTS = 5;                             // x ring: the four rows a two-row step reads + the one that comes in meanwhile
+constexpr int WRP_WPITCH = WRW_SW / 2 + 1;               // windows of a dy plane: the strip's 16 + 1 ("banks" below)
+constexpr int WRP_QPLANE = WRP_WPITCH * WRS16_PIX;       // 544 B: [17 windows][16 channels] of one piece, one 16-channel quarter
+constexpr int WRP_PLANE = 4 * WRP_QPLANE;                // 2176 B
+constexpr int WRP_ABUF = 4 * WRP_PLANE;                  // 8704 B: hi, mid, lo and the argmax codes (16 bits a channel), one window row
+constexpr int WRP_LDS = WRP_SLOTS * WRS16_SLOT + WRP_ABUF;   // 75904 B: two workgroups per CU in 160 KB
+constexpr int WRP_FLUSH = WRS_FLUSH / 2;                 // two-row steps a chain runs: the same 1024 pixels
+
+// THE image of a window row of dy: byte offset of channel `ch` (0 .. 15) of quarter `quarter` at window `window` of plane `plane`
+// (0 .. 2 the pieces, 3 the codes)
+__host__ __device__ constexpr int wrp_aoff(int plane, int quarter, int window, int ch) {
+    return plane * WRP_PLANE + quarter * WRP_QPLANE + window * WRS16_PIX + ch * 2;
+}
+// THE order of the GEMM's 64 k inside a sparse MFMA: k < 32 is the strip's row r, k >= 32 its row r + 1, and within a row the pixel is
+// the dense form's (a B operand is two of its fragments, hk_smfmac_bf16.h): aligned runs of four k are aligned runs of four pixels -
+// two windows, so a group of four of dy holds at most two non-zeros, the first at position 0 or 1 and the second at 2 or 3
+__host__ __device__ constexpr int wrp_krow(int k) { return k >> 5; }
+__host__ __device__ constexpr int wrp_kpix(int k) { return wrs16_kpix((k & 31) >> 3, k & 7); }
+// the window (0 .. 15) under value j of the A operand of a lane of group g: the lane's two transposing reads fetch windows
+// 4 (g % 2) ..+3 and 8 + 4 (g % 2) ..+3, and the dwords are taken in the order 0, 2, 1, 3
+__host__ __device__ constexpr int wrp_awin(int g, int j) { return 4 * (g & 1) + 8 * ((j >> 1) & 1) + 2 * (j >> 2) + (j & 1); }
+//   banks    = a 32-lane half of a transposing read of dy covers windows 0 .. 7 or 8 .. 15 of one quarter plane: 256 contiguous bytes
+//              from a multiple of 32, every bank once.  The 8-byte stores of a 16-lane group are one window's four quarters, 32 bytes
+//              each: with 17 windows (136 dwords) to a plane they start 8 banks apart.  Both static_asserted, with the k order:
+constexpr bool wrp_k_is_a_permutation() {
+    unsigned long long seen = 0;
+    for (int g = 0; g < 4; ++g)
+        for (int e = 0; e < 16; ++e) {
+            const int k = smfmac_b_k(g, e);
+            seen |= 1ull << (32 * wrp_krow(k) + wrp_kpix(k));
+        }
+    return seen == ~0ull;
+}
+constexpr bool wrp_groups_are_window_pairs() {
+    for (int k = 0; k < 64; k += 4)
+        for (int d = 0; d < 4; ++d)
+            if (wrp_kpix(k) % 4 != 0 || wrp_kpix(k + d) != wrp_kpix(k) + d || wrp_krow(k + d) != wrp_krow(k)) return false;
+    for (int g = 0; g < 4; ++g)                          // ... and value j of the A operand is the window wrp_awin says
+        for (int j = 0; j < 8; ++j)
+            if (wrp_kpix(smfmac_a_k4(g, j) + 2 * (j & 1)) / 2 != wrp_awin(g, j) || wrp_krow(smfmac_a_k4(g, j)) != g >> 1) return false;
+    return true;
+}
+constexpr bool wrp_a_reads_conflict_free() {
+    for (int plane = 0; plane < 4; ++plane)
+        for (int quarter = 0; quarter < 4; ++quarter)
+            for (int rd = 0; rd < 2; ++rd)
+                for (int half = 0; half < 2; ++half) {
+                    unsigned long long seen = 0;
+                    for (int l = 32 * half; l < 32 * half + 32; ++l) {
+                        const int g = l >> 4, i = l & 15;
+                        const int a = wrp_aoff(plane, quarter, 4 * (g & 1) + 8 * rd + (i >> 2), 4 * (i & 3));
+                        if (a % 8 != 0) return false;
+                        for (int d = 0; d < 2; ++d) {
+                            const int bank = (a / 4 + d) % 64;
+                            if ((seen >> bank) & 1ull) return false;
+                            seen |= 1ull << bank;
+                        }
+                    }
+                }
+    return true;
+}
+constexpr bool wrp_a_stores_conflict_free() {
+    for (int grp = 0; grp < 16; ++grp) {                 // a thread's float4: window tid / 16, quarter (tid / 4) % 4
+        unsigned seen = 0;
+        for (int tid = 16 * grp; tid < 16 * grp + 16; ++tid) {
+            const int a = wrp_aoff(0, (tid >> 2) & 3, tid >> 4, 4 * (tid & 3));
+            for (int d = 0; d < 2; ++d) {
+                const int bank = (a / 4 + d) % 32;
+                if ((seen >> bank) & 1u) return false;
+                seen |= 1u << bank;
+            }
+        }
+    }
+    return true;
+}
+static_assert(wrp_k_is_a_permutation(), "the four groups' B operands hold the 32 pixels of both rows once each");
+static_assert(wrp_groups_are_window_pairs(), "an aligned group of four k is two whole windows of one row");
+static_assert(wrp_a_reads_conflict_free(), "both 32-lane halves of both transposing reads of a pooled dy fragment cover the 64 banks once");
+static_assert(wrp_a_stores_conflict_free(), "every 16-lane group of a pooled dy staging store covers the 32 banks once");
+static_assert(2 * WRP_LDS <= 160 * 1024, "two workgroups per CU");
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+
+// the eight 16-bit values of plane `pl` (its bytes at the lane's quarter) under this lane's eight kept positions, as four dwords in
+// value order.  On the device two transposing reads, elsewhere the same values one by one.
+__device__ __forceinline__ u32x4 wrp_read(const char* pl, int g, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) bf16x4* lds_b64;
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const char* a = pl + wrp_aoff(0, 0, 4 * (g & 1) + (i >> 2), 4 * (i & 3));
+    const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)a));
+    const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64)(a + 8 * WRS16_PIX)));
+    return (u32x4){lo[0], hi[0], lo[1], hi[1]};
+#else
+    unsigned short v[8];
+    for (int j = 0; j < 8; ++j) __builtin_memcpy(&v[j], pl + wrp_aoff(0, 0, wrp_awin(g, j), i), 2);
+    u32x4 r;
+    for (int q = 0; q < 4; ++q) r[q] = (unsigned)v[2 * q] | ((unsigned)v[2 * q + 1] << 16);
+    return r;
+#endif
+}
+// One A operand: the three pieces of the eight windows under this lane's sixteen pixels, for output channel i of the quarter at `ab`,
+// and their positions.  A window's value is kept where its code's row bit is the lane's row (g / 2), else it is a zero; its position is
+// 2 (window % 2) + the code's column bit.
+__device__ __forceinline__ void wrp_afrag(const char* ab, int g, int i, bf16x8 (&a)[3], int& idx) {
+    const u32x4 c = wrp_read(ab + wrp_aoff(3, 0, 0, 0), g, i);
+    const u32x4 keep = (((c >> 1) & 0x00010001u) ^ ((g >> 1) ? 0u : 0x00010001u)) * 0xffffu;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) a[s] = __builtin_bit_cast(bf16x8, wrp_read(ab + wrp_aoff(s, 0, 0, 0), g, i) & keep);
+    const u32x4 nib = 8u | (c & 1u) | ((c >> 14) & 4u);
+    idx = (int)(nib[0] | (nib[1] << 4) | (nib[2] << 8) | (nib[3] << 12));
+}
+// HK_LOAD16_ASYNC / HK_LOAD4_ASYNC from a wave-uniform base (scalar registers) and a 32-bit byte offset per lane: the row's address is
+// made once per wave, and no thread carries six 64-bit row pointers through the MFMAs (they were the kernel's spills)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WRP_LOAD16(dst, base, off) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base) : "memory")
+#define WRP_LOAD4(dst, base, off) asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base) : "memory")
+#else
+#define WRP_LOAD16(dst, base, off) __builtin_memcpy(&(dst), reinterpret_cast<const char*>(base) + (off), 16)
+#define WRP_LOAD4(dst, base, off) __builtin_memcpy(&(dst), reinterpret_cast<const char*>(base) + (off), 4)
+#endif
+// this thread's loads of a window row of dy: window tid / 16 of the strip, channels 4 (tid % 16) ..+3
+struct WrpStage {
+    int doff, coff;                                      // bytes into dp / p and into the codes (a dword's), from the window row's start
+    int xoff[3];                                         // bytes into x from the row's start (WrwStage's, in 32 bits: a row is below 2^31)
+    bool dok;
+};
+__device__ __forceinline__ bool wrp_load_x(const float* __restrict__ xi, const WrpStage& sa, int r, int H, int W, int cin, f32x4 (&v)[3]) {
+    const bool rok = r >= 0 && r < H;
+    const float* row = xi + (long long)(r < 0 ? 0 : (r < H ? r : H - 1)) * W * cin;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) WRP_LOAD16(v[u], row, sa.xoff[u]);
+    return rok;
+}
+__device__ __forceinline__ void wrp_load_a(const float* __restrict__ dpi, const float* __restrict__ pi, const uint8_t* __restrict__ ami,
+                                           const WrpStage& sa, int ho, int Ho, int Wo, int Cout, f32x4& vd, f32x4& vp, unsigned& vc) {
+    const long long row = (long long)(ho < Ho ? ho : Ho - 1) * Wo;
+    WRP_LOAD16(vd, dpi + row * Cout, sa.doff);
+    WRP_LOAD16(vp, pi + row * Cout, sa.doff);
+    WRP_LOAD4(vc, ami + row * (Cout / 4), sa.coff);
+}
+// the rule of bias_relu_pool_bwd_kernel, applied before the split: a masked value is an exact zero
+__device__ __forceinline__ f32x4 wrp_mask(const WrpStage& sa, const f32x4& vd, const f32x4& vp) {
+    f32x4 d;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) d[t] = (sa.dok && !(vp[t] <= 0.f)) ? vd[t] : 0.f;
+    return d;
+}
+__device__ __forceinline__ void wrp_store_a(char* ab, const f32x4& d, unsigned vc) {
+    const int tid = threadIdx.x;
+    char* dst = ab + wrp_aoff(0, (tid >> 2) & 3, tid >> 4, 4 * (tid & 3));
+    wrs_store(dst, WRP_PLANE, d);
+    const unsigned code = (vc >> (8 * (tid & 3))) & 0xffu;
+    *reinterpret_cast<u16x4*>(dst + 3 * WRP_PLANE) = (u16x4){(unsigned short)(code & 3u), (unsigned short)((code >> 2) & 3u),
+                                                            (unsigned short)((code >> 4) & 3u), (unsigned short)(code >> 6)};
+}
+
+// dp, p [N][H/2][W/2][Cout], am [N][H/2][W/2][Cout/4], x [N][H][W][Cin] -> part [gridDim.x][Cout][9][Cin]: what
+// conv3x3_wrw_split_kernel<WIDE, WRS_MF_16> gives for the dy that bias_relu_pool_bwd_kernel makes of (dp, p, am), which is never formed.
+// Same grid, jobs (row blocks of an even height), x row image, borders, partial results and order of the six products.  A step is one
+// window row = two image rows: per tap ONE sparse MFMA per 16 x 16 block and product sums over the strip's 32 pixels of both rows (12
+// per (tap, block of input channels) where the dense form issues 24).  The B operand of tap (kh, kw) is the dense form's x fragment of
+// row r + kh - 1 followed by that of row r + kh, so the fragment of a row serves two taps: per (kw, block) the four rows' fragments are
+// read once for three taps.  The x ring has five slots: row r + 3 goes into the free one half way through the step's MFMAs, row r + 4
+// and the next window row of dy (one buffer: its fragments are in registers from the step's start) behind a barrier after them -
+// two barriers per two rows.
+template <bool WIDE>
+__global__ __launch_bounds__(256, 2) void conv3x3_wrw_pooled_kernel(const float* __restrict__ dp, const float* __restrict__ p,
+                                                                 const uint8_t* __restrict__ am, const float* __restrict__ x,
+                                                                 float* __restrict__ part, int H, int W, int Cout, int nstrips, int nrb,
+                                                                 int rpb, int njobs, int Cin) {
+    HK_DYN_LDS16(ldsf);
+    char* xs = reinterpret_cast<char*>(ldsf);            // ring of five x row segments (wrs16_off)
+    char* as = xs + WRP_SLOTS * WRS16_SLOT;              // one window row of dy (wrp_aoff)
+    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int oh = wave >> 1, ch = wave & 1;
+    const int cin = WIDE ? Cin : WRW_CI;
+    const int slice = blockIdx.y, cslice = WIDE ? blockIdx.z : 0;
+    const int Ho = H / 2, Wo = W / 2;
+    const int jb = (int)((long long)blockIdx.x * njobs / gridDim.x), je = (int)((long long)(blockIdx.x + 1) * njobs / gridDim.x);
+
+    f32x4 acc4[9][2][2];                                 // [tap][block of 16 output channels][block of 16 input channels]
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc4[t][q >> 1][q & 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int aoff = wrp_aoff(0, 2 * oh, 0, 0), boff = wrs16_off(0, 2 * ch, 0, 0);
+    auto mine = [&]() {                                  // (as in conv3x3_wrw_split_kernel)
+        const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+        return part + ((long long)blockIdx.x * Cout + slice * WRW_OT + (w >> 1) * 32 + 4 * (l >> 4)) * (9 * cin) + cslice * WRW_CI + (w & 1) * 32 + (l & 15);
+    };
+    auto landed = [](f32x4 (&vx)[3]) {
+        __builtin_amdgcn_s_waitcnt(HK_VMCNT_IMM(0));
+#pragma unroll
+        for (int u = 0; u < 3; ++u) HK_PIN_LOADED(vx[u]);
+    };
+    int since = 0;
+    bool stored = false;
+
+    for (int j = jb; j < je; ++j) {
+        const int strip = j % nstrips, jr = j / nstrips;
+        const int rb = jr % nrb;
+        const long long n = jr / nrb;
+        const int c0 = strip * WRW_SW, r0 = rb * rpb;
+        const int nsteps = ((r0 + rpb < H ? r0 + rpb : H) - r0) / 2;
+        const float* xi = x + n * H * W * cin + cslice * WRW_CI;
+        const float* dpi = dp + n * Ho * Wo * Cout + slice * WRW_OT;
+        const float* pi = p + n * Ho * Wo * Cout + slice * WRW_OT;
+        const uint8_t* ami = am + n * Ho * Wo * (Cout / 4) + slice * (WRW_OT / 4);
+        WrwStage st;                                     // (its xok alone: the staging stores')
+        WrpStage sa;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int idx = tid + 256 * u, col = c0 - 1 + (idx >> 4);
+            st.xok[u] = idx < WRW_XF4 && col >= 0 && col < W;
+            sa.xoff[u] = 4 * ((col < 0 ? 0 : (col < W ? col : W - 1)) * cin + 4 * (idx & 15));
+        }
+        {
+            const int wcol = c0 / 2 + (tid >> 4);
+            sa.dok = wcol < Wo;
+            sa.doff = 4 * ((wcol < Wo ? wcol : Wo - 1) * Cout + 4 * (tid & 15));
+            sa.coff = (wcol < Wo ? wcol : Wo - 1) * (Cout / 4) + ((tid & 15) & ~3);
+        }
+        // the first step's operands: x rows r0 - 1 .. r0 + 2 into slots 0 .. 3 and window row r0 / 2 (the barrier that ended the previous
+        // job's last step has every wave past its reads)
+        f32x4 vx[3], vd, vp;
+        unsigned vc;
+        wrp_load_a(dpi, pi, ami, sa, r0 / 2, Ho, Wo, Cout, vd, vp, vc);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool rok = wrp_load_x(xi, sa, r0 - 1 + t, H, W, cin, vx);
+            landed(vx);
+            wrs16_store_x(xs, t, st, rok, vx);
+        }
+        HK_PIN_LOADED(vd); HK_PIN_LOADED(vp); HK_PIN_LOADED(vc);
+        wrp_store_a(as, wrp_mask(sa, vd, vp), vc);
+        __syncthreads();
+        int base = 0;                                    // slot of x row r - 1 of the step
+        for (int s = 0; s < nsteps; ++s) {               // rows r = r0 + 2 s and r + 1: x rows r - 1 .. r + 2 are slots base .. base + 3 (mod 5)
+            const int r = r0 + 2 * s;
+            bool rok = wrp_load_x(xi, sa, r + 3, H, W, cin, vx);
+            wrp_load_a(dpi, pi, ami, sa, r / 2 + 1, Ho, Wo, Cout, vd, vp, vc);
+            const char* B[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) B[t] = xs + ((base + t) % WRP_SLOTS) * WRS16_SLOT + boff;
+            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
+            bf16x8 a[2][3];
+            int idx[2];
+#pragma unroll
+            for (int ob = 0; ob < 2; ++ob) wrp_afrag(as + aoff + wrp_aoff(0, ob, 0, 0), g, l15, a[ob], idx[ob]);
+            // 18 rounds of twelve MFMAs: (kw, block of 16 input channels) x kh.  A piece's fragment of the next round is read as soon as the
+            // piece has had its last product of this round: lo after the second, mid after the fourth, hi at the end
+            bf16x16 b[3];
+#pragma unroll
+            for (int sp = 0; sp < 3; ++sp)
+                b[sp] = __builtin_shufflevector(wrs16_frag(B[0] + wrs16_off(sp, 0, 0, 0), g, l15), wrs16_frag(B[1] + wrs16_off(sp, 0, 0, 0), g, l15),
+                                                0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+#pragma unroll
+            for (int i = 0; i < 18; ++i) {
+                const int kw = i / 6, cb = (i / 3) % 2, kh = i % 3, t = 3 * kh + kw;
+                const int kwn = (i + 1) / 6, cbn = ((i + 1) / 3) % 2, khn = (i + 1) % 3;
+                auto next = [&](int sp) {                // piece sp of round i + 1: the upper row moves down and row kh + 2 comes in, or two new rows
+                    if (i + 1 == 18) return;
+                    const bf16x8 up = wrs16_frag(B[khn + 1] + wrs16_off(sp, cbn, kwn, 0), g, l15);
+                    if (khn > 0)
+                        b[sp] = __builtin_shufflevector(b[sp], __builtin_shufflevector(up, up, 0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7),
+                                                        8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23);
+                    else
+                        b[sp] = __builtin_shufflevector(wrs16_frag(B[0] + wrs16_off(sp, cbn, kwn, 0), g, l15), up,
+                                                        0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+                };
+#pragma unroll
+                for (int pr = 0; pr < 6; ++pr) {
+#pragma unroll
+                    for (int ob = 0; ob < 2; ++ob)
+                        acc4[t][ob][cb] = smfmac_f32_16x16x64_bf16(a[ob][PA[pr]], b[PB[pr]], acc4[t][ob][cb], idx[ob]);
+                    if (pr == 1 || pr == 3 || pr == 5) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        next(pr == 1 ? 2 : (pr == 3 ? 1 : 0));
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if (i == 8) {                            // row r + 3 into the free slot, row r + 4 on its way; dp and p become one value
+                    landed(vx);
+                    HK_PIN_LOADED(vd); HK_PIN_LOADED(vp); HK_PIN_LOADED(vc);
+                    vd = wrp_mask(sa, vd, vp);
+                    wrs16_store_x(xs, (base + 4) % WRP_SLOTS, st, rok, vx);
+                    rok = wrp_load_x(xi, sa, r + 4, H, W, cin, vx);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            __syncthreads();                             // every wave has read rows r - 1, r and - long ago - the dy buffer
+            landed(vx);
+            wrs16_store_x(xs, base, st, rok, vx);
+            wrp_store_a(as, vd, vc);
+            __syncthreads();
+            base = (base + 2) % WRP_SLOTS;
+            if (++since == WRP_FLUSH) {
+                wrs16_flush(mine(), acc4, stored, cin);
+                since = 0;
+                stored = true;
+            }
+        }
+    }
+    if (since > 0 || !stored) wrs16_flush(mine(), acc4, stored, cin);
+}
+
+// Which calls the pooled form serves by default (knob wrw_pool at -1), decided by the layers' times inside the training step
+// (profiles/wrw_pool_step_layers.json: HK_WRW_POOL=0 against the default on this build): all five pooled layers of VGG-16 at 448 x 448 are
+// faster at batch 64 (0.65 - 0.68 x the dense kernel's time, the slowest repeat below the dense kernel's fastest) and at batch 16
+// (0.36 - 0.68 x).  The rule is "always" from the smallest map that was measured (conv5_3 at batch 16: 16 x 28 x 28 pixels) and
+// nothing below it, which nobody has timed; `wrw_pool` 1 reaches the kernel at every served shape (tests).
+static bool wrw_pool_wins(int N, int H, int W, int Cin, int Cout) {
+    (void)Cin; (void)Cout;
+    return (long long)N * H * W >= 16ll * 28 * 28;
+}
+
+template <bool WIDE>
+static int wrw_pooled_launch(dim3 grid, const float* dp, const float* p, const uint8_t* am, const float* x, float* part, int H, int W,
+                             int Cout, const WrwPlan& pl, int cin, hk_stream_t stream) {
+    HK_ALLOW_BIG_LDS((conv3x3_wrw_pooled_kernel<WIDE>), WRP_LDS);
+    hipLaunchKernelGGL((conv3x3_wrw_pooled_kernel<WIDE>), grid, dim3(256), WRP_LDS, (hipStream_t)stream, dp, p, am, x, part, H, W, Cout,
+                       pl.nstrips, pl.nrb, pl.rpb, pl.njobs, cin);
+    HK_LAUNCH_CHECK();
+    return HK_OK;
+}
+
+// the shapes the pooled form runs on: hk_conv3x3_wrw's wide split form's, and whole windows
+static bool wrw_pooled_shape_ok(int N, int H, int W, int Cin, int Cout) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return false;
+    if (Cin % WRW_CI != 0 || Cout % WRW_OT != 0 || Cout / WRW_OT > 65535 || Cin / WRW_CI > 65535 || (long long)Cout * 9 * Cin > 0x7fffffffll) return false;
+    if ((long long)(Cout / WRW_OT) * (Cin / WRW_CI) > 0x7fffffffll) return false;
+    // WrpStage's lane offsets are 32-bit bytes from a row's start: a row of x and a window row of dp / p stay below 2^31 bytes
+    if ((long long)W * Cin * 4 > 0x7fffffffll || (long long)(W / 2) * Cout * 4 > 0x7fffffffll) return false;
+    return H % 2 == 0 && W % 2 == 0;
 }
 
 }  // namespace hk
@@ -760,6 +1126,46 @@ extern "C" int hk_conv3x3_wrw(const float* dy, const float* x, float* dw, int N,
                            part, H, W, Cout, pl.nstrips, pl.nrb, pl.rpb, pl.njobs);
     }
     HK_LAUNCH_CHECK();
+    const int nel = Cout * 9 * Cin;
+    hipLaunchKernelGGL(partial_sum_kernel<16>, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, pl.nwg, nel, nel,
+                       dw, (float*)nullptr);
+    HK_LAUNCH_CHECK();
+    return HK_OK;
+}
+
+// ---- hawkeye_conv_pool.h ----
+// the one reader of the knob wrw_pool and its rule
+extern "C" int hk_conv3x3_wrw_pooled_served(int N, int H, int W, int Cin, int Cout) {
+    const int pool = tuning().wrw_pool;
+    if (pool == 0 || tuning().wrw_split == 0 || tuning().wrw_wide == 0 || !wrw_pooled_shape_ok(N, H, W, Cin, Cout)) return 0;
+    return pool > 0 || wrw_pool_wins(N, H, W, Cin, Cout) ? 1 : 0;
+}
+
+extern "C" int hk_conv3x3_wrw_pooled_plan(int N, int H, int W, int Cin, int Cout, int* out) {
+    if (!out) return HK_ERR_BAD_ARG;
+    if (!wrw_pooled_shape_ok(N, H, W, Cin, Cout)) return HK_ERR_UNSUPPORTED;
+    WrwPlan pl;
+    if (!wrw_plan(N, H, W, (Cout / WRW_OT) * (Cin / WRW_CI), true, pl, true)) return HK_ERR_UNSUPPORTED;
+    out[0] = pl.nstrips; out[1] = pl.nrb; out[2] = pl.rpb; out[3] = pl.njobs; out[4] = pl.nwg;
+    return HK_OK;
+}
+
+extern "C" int hk_conv3x3_wrw_pooled(const float* dp, const float* p, const uint8_t* argmax, const float* x, float* dw, int N, int H, int W,
+                                     int Cin, int Cout, void* ws, size_t ws_bytes, hk_stream_t stream) {
+    if (!dp || !p || !argmax || !x || !dw || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return HK_ERR_BAD_ARG;
+    if (!ws || ws_bytes < hk_conv3x3_wrw_ws_bytes(Cin, Cout)) return HK_ERR_WORKSPACE;
+    if (!wrw_pooled_shape_ok(N, H, W, Cin, Cout) || !aligned16(dp) || !aligned16(p) || !aligned16(argmax) || !aligned16(x) || !aligned16(dw) ||
+        !aligned16(ws) || tuning().wrw_split == 0 || tuning().wrw_wide == 0)
+        return HK_ERR_UNSUPPORTED;
+    // (the plan and the workspace of a WIDE call at every Cin: with one Cin slice that is wrw_wide_wgs(Cout slices) <= WRW_MAX_WG workgroups)
+    const int oslices = Cout / WRW_OT, cslices = Cin / WRW_CI;
+    WrwPlan pl;
+    if (!wrw_plan(N, H, W, oslices * cslices, true, pl, true)) return HK_ERR_UNSUPPORTED;
+    float* part = (float*)ws;
+    const dim3 grid((unsigned)pl.nwg, (unsigned)oslices, (unsigned)cslices);
+    const int e = Cin > WRW_CI ? wrw_pooled_launch<true>(grid, dp, p, argmax, x, part, H, W, Cout, pl, Cin, stream)
+                               : wrw_pooled_launch<false>(grid, dp, p, argmax, x, part, H, W, Cout, pl, WRW_CI, stream);
+    if (e != HK_OK) return e;
     const int nel = Cout * 9 * Cin;
     hipLaunchKernelGGL(partial_sum_kernel<16>, dim3((nel + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)part, pl.nwg, nel, nel,
                        dw, (float*)nullptr);

@@ -65,6 +65,9 @@ struct Tuning {
     int wrw_wide = 1;       // HK_WRW_WIDE      hk_conv3x3_wrw with more than 64 input channels (split form only): 1: served, 0: refused (HK_ERR_UNSUPPORTED)
     int wrw_mfma = -1;      // HK_WRW_MFMA      bf16 MFMA of hk_conv3x3_wrw's split form (conv_wrw.hip, MF): 1: v_mfma_f32_16x16x32_bf16, 0: v_mfma_f32_32x32x16_bf16,
                             //                  -1: per call, the measured winner (conv_wrw.hip: wrw_mfma16_wins)
+    int wrw_pool = -1;      // HK_WRW_POOL      weight gradient of a 3 x 3 layer that ends in a 2 x 2 max-pool, from the pooled gradient on the 2:4 sparse
+                            //                  MFMA (hk_conv3x3_wrw_pooled, conv_wrw.hip): 0: never, 1: wherever served, -1: the measured winner
+                            //                  (conv_wrw.hip: wrw_pool_wins); read by hk_conv3x3_wrw_pooled_served alone
     int conv_fwd = -1;      // HK_CONV_FWD     forward of the trunk's 3 x 3 convolutions with multiples of 64 channels: -1: hk_conv3x3_fwd for the layers of the
                             //                  measured table (functional.CONV_FWD_WINS), 0: the library's everywhere (the entry point refuses), 1: hk_conv3x3_fwd
                             //                  wherever it serves the call (tests)

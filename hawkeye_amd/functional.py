@@ -2270,6 +2270,27 @@ def conv3x3_wrw_raw(x, dy):
     return buf.permute(0, 3, 1, 2)
 
 
+def conv3x3_wrw_pooled_raw(x, dp, p, aux):
+    """dW as conv3x3_wrw_raw(x, g) gives it for the g that hk_bias_relu_pool_bwd makes of the pooled gradient dp [N, Cout, H/2, W/2], the
+    pooled output p and the forward's argmax codes aux [N, H/2, W/2, Cout/4] - without g (hk_conv3x3_wrw_pooled: the 2:4 sparse
+    MFMA, half the matrix instructions); raises where the entry point does not serve the call."""
+    lib = _lib.load()
+    _nhwc(x, 'conv3x3_wrw_pooled')
+    _nhwc(dp, 'conv3x3_wrw_pooled')
+    _nhwc(p, 'conv3x3_wrw_pooled')
+    n, cin, h, w = x.shape
+    cout = dp.shape[1]
+    if (h % 2 or w % 2 or tuple(dp.shape) != (n, cout, h // 2, w // 2) or tuple(p.shape) != tuple(dp.shape) or aux.dtype != torch.uint8
+            or tuple(aux.shape) != (n, h // 2, w // 2, cout // 4) or x.numel() == 0 or dp.numel() == 0):
+        raise _lib.HawkeyeHipError(f'conv3x3_wrw_pooled: dp {tuple(dp.shape)}, p {tuple(p.shape)}, codes {tuple(aux.shape)} do not match x {tuple(x.shape)}')
+    px, pdp, pp, pa = ptr(x), ptr(dp), ptr(p), ptr(aux)
+    buf = torch.empty(cout, 3, 3, cin, dtype=torch.float32, device=x.device)
+    nws = lib.hk_conv3x3_wrw_ws_bytes(cin, cout)
+    ws = _ws(nws, x.device)
+    check(lib.hk_conv3x3_wrw_pooled(pdp, pp, pa, px, ptr(buf), n, h, w, cin, cout, ptr(ws), nws, stream()), 'hk_conv3x3_wrw_pooled')
+    return buf.permute(0, 3, 1, 2)
+
+
 # The layers whose forward goes to hk_conv3x3_fwd, and whose input gradient goes to hk_conv3x3_bwd_data, by default (knobs `conv_fwd` /
 # `conv_bwd_data` at -1): (Cin, Cout, H, W) -> the batch sizes at which the kernel was measured against the library's kernel of that
 # layer and direction and won, stand-alone (profiles/conv_split_timing.json: slowest repeat faster than the library's fastest by more
@@ -2564,7 +2585,12 @@ class _ConvUnit(torch.autograd.Function):
             else:
                 dx = conv3x3_bwd_data_raw(g, weight)
         if need_dw and wrw:
-            dw = conv3x3_wrw_raw(x, g)
+            # a pooled layer's g is three quarters zeros by construction: where the library says so (knob `wrw_pool`), dW comes from the
+            # pooled gradient itself on the 2:4 sparse MFMA; g stays what the input gradient and db are made of
+            if pool and lib.hk_conv3x3_wrw_pooled_served(n, h, w, cin, cout):
+                dw = conv3x3_wrw_pooled_raw(x, dy, p, aux)
+            else:
+                dw = conv3x3_wrw_raw(x, g)
         lib_mask = (need_dx and not bwd, need_dw and not wrw, False)
         if lib_mask[0] or lib_mask[1]:
             r = torch.ops.aten.convolution_backward(g, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, lib_mask)

@@ -73,6 +73,8 @@ const char* hk_version(void);
  *                   HK_ERR_UNSUPPORTED, as before the split form read wider pixels
  *   "wrw_mfma"      the bf16 MFMA the split form of hk_conv3x3_wrw runs on: 1 = v_mfma_f32_16x16x32_bf16, 0 = v_mfma_f32_32x32x16_bf16,
  *                   -1 (default) = per call, the measured winner (a rule in N, H, W and Cout).  Same bound either way; the bits differ
+ *   "wrw_pool"      weight gradient of a 3 x 3 layer that ends in a 2 x 2 max-pool, straight from the pooled gradient on the 2:4 sparse
+ *                   bf16 MFMA (hawkeye_conv_pool.h): 0 = never, 1 = wherever served, -1 (default) = per layer, the measured winner
  *   "conv_fwd"      forward of the trunk's 3 x 3 convolutions with multiples of 64 channels (hawkeye_conv.h): -1 (default) = the split
  *                   bf16-MFMA kernel for the layers of the measured table, 0 = the library's everywhere (the entry point then refuses
  *                   with HK_ERR_UNSUPPORTED), 1 = the kernel wherever the entry point serves the call (tests)
@@ -677,6 +679,7 @@ int hk_bgemm_f32(const float* a, int lda, long long stride_a, int trans_a, const
 #include "hawkeye_conv.h" /* the trunk's forward and input gradient */
 #include "hawkeye_conv_epi.h" /* ... with the trunk's epilogue passes done inside those kernels */
 #include "hawkeye_conv_tile.h" /* ... and how those kernels tile a map */
+#include "hawkeye_conv_pool.h" /* the weight gradient of the trunk's pooled layers from the pooled gradient */
 #include "hawkeye_interp.h" /* the InterpParts plugin: region grouping and the shaping loss */
 #include "hawkeye_mge.h" /* the MGE-CNN plugin: part pool, Grad-CAM box and the criterion */
 
