@@ -445,8 +445,8 @@ int hk_linear_bwd(const float* y, const float* w, const float* g, float* dy, flo
                   hk_stream_t stream);
 /* With a per-sample scale folded in (row_scale [B], e.g. the 1 / |z| of a pooled vector handed over unnormalised):
  *   out = row_scale[b] * (y W^T) + bias ;  dy = g W  (= dL/d(row_scale y)) ;  dW = (row_scale g)^T y ;  db = sum_b g.
- * hk_linear_bwd_scaled is served by the one-launch kernel only (up to 64 samples, up to 208 outputs, J % 64 == 0,
- * J >= 16384); HK_ERR_UNSUPPORTED - nothing launched - otherwise. */
+ * hk_linear_bwd_scaled is served by the one-launch kernel only (up to 64 samples, up to 208 outputs, J % 4 == 0,
+ * J >= 4096); HK_ERR_UNSUPPORTED - nothing launched - otherwise. */
 int hk_linear_fwd_scaled(const float* y, const float* w, const float* bias, const float* row_scale, float* out, int B, int J,
                          int K, void* ws, size_t ws_bytes, hk_stream_t stream);
 int hk_linear_bwd_scaled(const float* y, const float* w, const float* g, const float* row_scale, float* dy, float* dw, float* db,
